@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- the benchmarks of BASELINE.json on MI355X.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5] [--scaling strong|weak]
+  python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5] [--scaling strong|weak] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds everything else below: the
+cpu_baseline, the legs and other_configs.  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
 
 config 2 (default, the headline): DEFLATE level-6 100 000 x 64 KiB entries, inflate + fused CRC-32 (k_inflate_batch)
 config 3: DEFLATE level-6 1 000 000 x 8 KiB entries, same kernel (the small-entry shape of the 8-GPU sharding config)
@@ -24,7 +27,7 @@ data    : synthetic, SURVEY 8(d): entries are slices of C = appnote.txt || appno
           (100 000 unique slices, ~240 core-seconds of level-6 compression spread over all host cores; config 3: 524 288
           unique slices of the corpus + 4 MiB of its 4 KiB pieces in random order, config 4: 1 024 unique 1 MiB streams), compressed with exactly the reference writer's parameters
           (mz_strm_zlib.c:87: raw, 32 KiB window, memLevel 8 -- the cpu_baseline leg checks that the reference writer
-          emits the same bytes).  Only when the host is too slow (--gen-seconds runs out) the streams made so far are
+          emits the same bytes).  Only when --gen-seconds is given and runs out the streams made so far are
           tiled to the entry count, and `data` says how many were tiled; every entry has its own copy of its compressed
           bytes and its own output region in HBM either way.
 
@@ -36,12 +39,12 @@ Besides the contract fields the JSON line carries
                  (size x count) of the committed rocprofv3 --pmc passes named in `traffic_source`, `traffic_raw` what
                  FETCH_SIZE + WRITE_SIZE say of the same passes (gfx950 tallies 128-byte reads at 64), both null when the
                  passes were taken on another workload shape;
-  cpu_baseline : the UNMODIFIED reference path (oracle/_ref) on the host cores of the same box, on a bounded sample of
+  cpu_baseline : (--full) the UNMODIFIED reference path (oracle/_ref) on the host cores of the same box, on a bounded sample of
                  the same workload.  Rank 0, N = 1 only;
-  other_configs: (the default run: config 2, N = 1) BASELINE.json configs[2], [3], [4] -- `--config 3`, `4`, `5` run as child
+  other_configs: (--full, config 2, N = 1) BASELINE.json configs[2], [3], [4] -- `--config 3`, `4`, `5` run as child
                  processes behind the headline, each condensed to value, ms_per_step, crc32_match_rate, unique streams,
                  roofline {achieved, frac, traffic, traffic_source} and cpu_baseline;
-  legs         : (config 2, N = 1) SURVEY 8(d) i-iii: kernel only / H2D of the compressed bytes + kernel + D2H of
+  legs         : (--full, config 2, N = 1) SURVEY 8(d) i-iii: kernel only / H2D of the compressed bytes + kernel + D2H of
                  {crc, len, status} from pinned host memory / the reference's unmodified mz_zip_reader loop on the
                  drop-in library (prime + vtbl shims) into host buffers, GiB/s of decompressed bytes each; and ONE large entry
                  (512 MiB of the corpus at level 1) through the same reader loop, per entry (`one_large_entry_vtbl`: window
@@ -184,7 +187,7 @@ def shared_unique_deflate(c, n_unique, size, seed, gen_seconds, world, local_ran
         return offs, pays, crcs
     t0 = time.time()
     while not os.path.exists(path):
-        if time.time() - t0 > 4 * gen_seconds + 600:
+        if time.time() - t0 > 4 * min(gen_seconds, 900.0) + 600:
             fail("rank with LOCAL_RANK %d: the table of LOCAL_RANK 0 (%s) did not appear" % (local_rank, path))
         time.sleep(0.5)
     z = np.load(path)
@@ -284,6 +287,8 @@ def device_blob(torch, dev, pays, pick, align=16):
     ublob = np.zeros(int(uoff[-1] + upad[-1]), dtype=np.uint8)
     for i, p in enumerate(pays):
         ublob[uoff[i]:uoff[i] + len(p)] = np.frombuffer(p, dtype=np.uint8)
+    if n == len(pays) and (pick == np.arange(n)).all():  # every stream once, in order: the gather below would copy ublob
+        return torch.from_numpy(ublob).to(dev), ublob, in_off, in_len
     gran = (pad // 16).astype(np.int64)
     gstart = np.concatenate(([0], np.cumsum(gran)[:-1]))
     u16 = ublob.view(np.dtype((np.void, 16)))
@@ -748,7 +753,9 @@ def other_configs(args):
     out = {}
     for k in (3, 4, 5):
         cmd = [sys.executable, os.path.abspath(__file__), "--config", str(k), "--gpus", "1", "--steps", str(min(args.steps, 3)),
-               "--warmup", "1", "--no-legs", "--gen-seconds", str(args.gen_seconds)]
+               "--warmup", "1", "--full", "--no-legs"]
+        if args.gen_seconds is not None:
+            cmd += ["--gen-seconds", str(args.gen_seconds)]
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
         t0 = time.time()
@@ -770,6 +777,46 @@ def other_configs(args):
                                             "kernel_ms", "algorithmic_bytes_per_launch")},
             "cpu_baseline": j.get("cpu_baseline"), "wall_s": round(time.time() - t0, 1)}
     return out
+
+
+DUMP_LIMIT = 60_000_000  # bytes of every .npy file --dump-outputs writes, together
+
+
+def dump_outputs(path, suffix, torch, last, d_out, width, n):
+    """--dump-outputs: what a caller of the timed path received from its last step.  The per-entry results (out_len,
+    in_used, crc32, status) as float64, exact for every int32 / uint32 value; the output bytes of a fixed, seeded sample of
+    the entries as float32, one row of `width` bytes per entry with the bytes past its out_len zeroed (the rows' entry
+    numbers in out_bytes_rows).  When the per-entry results of every entry would take more than half of DUMP_LIMIT they
+    are sampled the same way (entry numbers in entry_rows).  The same arguments give the same inputs, so two builds can be
+    compared file for file."""
+    os.makedirs(path, exist_ok=True)
+    out_len, in_used, crc, status = last
+    res = [(k, t) for k, t in (("out_len", out_len), ("in_used", in_used), ("crc32", crc), ("status", status)) if t is not None]
+    rnd = np.random.RandomState(2024)
+    used = 0
+
+    def save(name, a, dtype):
+        nonlocal used
+        a = np.ascontiguousarray(a, dtype=dtype)
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+        used += a.nbytes
+
+    keep = min(n, DUMP_LIMIT // 2 // (8 * len(res)))
+    erows = np.arange(n) if keep == n else np.sort(rnd.choice(n, keep, replace=False))
+    if keep < n:
+        save("entry_rows", erows, np.float64)
+    lens = out_len.cpu().numpy().astype(np.int64)
+    for name, t in res:
+        a = t.cpu().numpy()
+        if name == "crc32":
+            a = a.view(np.uint32)  # the CRC's 32 bits, held in int32 storage
+        save(name, a[erows], np.float64)
+    k = max(1, min(n, min(32 << 20, DUMP_LIMIT - used) // (4 * width + 8)))
+    rows = np.sort(rnd.choice(n, k, replace=False))
+    got = d_out[:n * width].view(n, width)[torch.from_numpy(rows).to(d_out.device)].cpu().numpy()
+    got[np.arange(width)[None, :] >= np.clip(lens[rows], 0, width)[:, None]] = 0
+    save("out_bytes_rows", rows, np.float64)
+    save("out_bytes", got, np.float32)
 
 
 def fail(msg):
@@ -824,10 +871,16 @@ def main():
     ap.add_argument("--entries", type=int, default=0, help="entries of the table (strong) / per GPU (weak); 0 = the config's")
     ap.add_argument("--entry-size", type=int, default=0)
     ap.add_argument("--unique", type=int, default=0, help="max unique compressed slices to generate")
-    ap.add_argument("--gen-seconds", type=float, default=45.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="config 2, N = 1: do not run configs 3, 4, 5 behind the headline")
+    ap.add_argument("--gen-seconds", type=float, default=None,
+                    help="stop compressing after this many seconds and tile the streams made so far (default: no limit, "
+                         "so that the inputs are the same on every run)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the legs and (config 2, N = 1) configs 3, 4, 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64 / float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: no legs")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full, config 2, N = 1: do not run configs 3, 4, 5 behind the headline")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     if args.gpus < 1:
@@ -867,14 +920,15 @@ def main():
     # the worker pool that compresses the synthetic slices forks: do it before this process creates its HIP context
     # and the RCCL threads.  Strong scaling: every rank derives the SAME table (same seeds); weak: its own.
     seed = 1234 if strong else 1234 + rank
+    gen_seconds = float("inf") if args.gen_seconds is None else args.gen_seconds
     offs = datas = None
     if cfg["codec"] == "lzma":
-        datas, pays, crcs = make_markov_lzma(c, n_unique, size, seed, max(args.gen_seconds, 90.0), world)
+        datas, pays, crcs = make_markov_lzma(c, n_unique, size, seed, max(gen_seconds, 90.0), world)
     else:
         if strong and world > 1 and not os.environ.get("MZHIP_BENCH_NO_TABLE_CACHE"):
-            offs, pays, crcs = shared_unique_deflate(c, n_unique, size, seed, args.gen_seconds * cfg.get("gen_scale", 1.0), world, local, "c%d" % args.config)
+            offs, pays, crcs = shared_unique_deflate(c, n_unique, size, seed, gen_seconds * cfg.get("gen_scale", 1.0), world, local, "c%d" % args.config)
         else:
-            offs, pays, crcs = make_unique_deflate(c, n_unique, size, seed, args.gen_seconds * cfg.get("gen_scale", 1.0), world)
+            offs, pays, crcs = make_unique_deflate(c, n_unique, size, seed, gen_seconds * cfg.get("gen_scale", 1.0), world)
     # MZHIP_BENCH_SHARE_GPU=1 (tests/test_gpu_bench_ranks.py, a box with ONE GPU): every rank uses device 0 and the
     # collectives go through gloo on host copies -- the N > 1 logic (sharding, gather, reductions) on real kernels
     # where RCCL cannot run (it refuses two ranks on one device).  Never set by the driver: the product path is RCCL.
@@ -1008,6 +1062,7 @@ def main():
         out_len, in_used, crc, status = launch()
         if i_timed is not None:
             ev[i_timed][1].record()
+        stats["last"] = (out_len, in_used, crc, status)
         if world > 1:
             if i_timed is not None:
                 gev[i_timed][0].record()
@@ -1054,6 +1109,10 @@ def main():
             got = d_out[e * size:(e + 1) * size].cpu().numpy().tobytes()
             want = datas[pick[e]] if datas is not None else c[offs[pick[e]][0]:offs[pick[e]][0] + size]
             bytes_ok = bytes_ok and got == want
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "" if world == 1 else "_rank%d" % rank, torch, stats["last"], d_out,
+                     cap if cfg["codec"] == "deflate" else size, n)
 
     total_entries = n
     algo_all = float(algo_bytes)
@@ -1120,7 +1179,7 @@ def main():
         if world > 1:
             line["config"]["launch"]["gather_ms"] = round(gather_ms, 3)  # slowest rank, mean of the timed steps (waits for the slowest rank's launch)
         sample_zip = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cores = usable_cores()  # threads the CPU baseline really gets (affinity and cgroup quota, not the CPU count)
             if cfg["codec"] == "inflate":
                 sample_zip = os.path.join(tempfile.mkdtemp(prefix="mzhip_bench_"), "sample.zip")
@@ -1131,7 +1190,7 @@ def main():
                 cb = cpu_baseline_deflate(c, offs, size, cores)
             if cb is not None:
                 line["cpu_baseline"] = cb
-        if world == 1 and args.config == 2 and not args.no_legs:
+        if world == 1 and args.config == 2 and args.full and not args.no_legs:
             # the archive of leg (iii): 16 384 of the bench's own streams (1 GiB decoded), so that the prime pipeline has
             # something to pipeline; the reference writer's 2 048-entry sample of the cpu_baseline leg when that is all there is
             legs_zip = sample_zip
@@ -1162,7 +1221,7 @@ def main():
         if sample_zip and os.path.exists(sample_zip):
             os.remove(sample_zip)
             os.rmdir(os.path.dirname(sample_zip))
-        if world == 1 and args.config == 2 and not args.no_other_configs and not (args.entries or args.entry_size or args.unique):
+        if world == 1 and args.config == 2 and args.full and not args.no_other_configs and not (args.entries or args.entry_size or args.unique):
             # BASELINE.json configs[2..4] behind the headline, each as its own process (its own data, its own HIP context; this
             # process's tensors stay allocated: 9 GB of 288), each with its own roofline and cpu_baseline
             del d_in, d_out

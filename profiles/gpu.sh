@@ -97,7 +97,7 @@ evidence)
   name=$1; shift
   out=$root/gpurun_out/$name; mkdir -p $out
   cd $root
-  timeout 1500 python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+  timeout 1500 python bench.py --steps 20 --warmup 5 --full > $out/bench.json 2> $out/bench.err
   tail -c 600 $out/bench.err
   ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $out/stats -o k --output-format csv -- python $root/bench.py --steps 20 --warmup 5 --no-legs --no-cpu-baseline --no-other-configs > $out/bench_under_rocprof.json 2> $out/stats.err )
   find $out/stats -name '*kernel_stats.csv' -exec cp {} $out/kernel_stats.csv \;

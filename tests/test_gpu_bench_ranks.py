@@ -83,3 +83,29 @@ def test_more_gpus_than_the_box_has_is_an_error_not_a_smaller_run():
     assert r.returncode != 0
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and "error" in json.loads(lines[0]) and "value" not in json.loads(lines[0])
+
+
+def test_dump_outputs_of_the_last_step(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's per-entry results in full and a seeded sample of the decoded bytes,
+    float64 / float32, under 64 MB; the inputs do not depend on the run, so another step count dumps the same files."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MZHIP_BENCH_SHARE_GPU")}
+    dumps = []
+    for steps in ("3", "1"):
+        d = tmp_path / ("s" + steps)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", steps, "--warmup", "1",
+                            "--entries", "3001", "--unique", "256", "--dump-outputs", str(d)], cwd=ROOT, env=env,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == int(steps) and line["ms_per_step"] > 0 and line["crc32_match_rate"] == 1.0
+        assert "cpu_baseline" not in line and "legs" not in line and "other_configs" not in line
+        dumps.append({f.stem: np.load(f) for f in sorted(d.iterdir()) if f.suffix == ".npy"})
+    a, b = dumps
+    assert set(a) == {"out_len", "in_used", "crc32", "status", "out_bytes", "out_bytes_rows"}
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["out_bytes"].dtype == np.float32 and a["crc32"].dtype == np.float64 and a["crc32"].shape == (3001,)
+    assert (a["status"] == 0).all() and (a["out_len"] == 65536).all() and a["out_bytes"].shape[1] == 65536
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
