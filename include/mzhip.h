@@ -24,6 +24,19 @@
  * Status words are numerically the reference's (mz.h:21-26): 0 OK,
  * -3 MZ_DATA_ERROR, -5 MZ_BUF_ERROR (input ended early), plus
  * MZHIP_OUT_FULL (-200) when an entry produces more than its out_cap.
+ *
+ * Memory an entry may touch (every batch entry point; tests/test_gpu_bounds.py and the emulation tests hold each to it):
+ *   - it WRITES d_out + d_out_off[i] .. + d_out_cap[i] and element i of each result array, nothing else: not a byte in
+ *     front of its region, behind it (entries may lie back to back: out_off[i + 1] == out_off[i] + out_cap[i]) or in
+ *     the input, not an element n or beyond of a result array.  A match whose distance reaches in front of the entry's
+ *     own output is refused (-3) before a byte of it is copied;
+ *   - an entry that ends with status 0 leaves the bytes [d_out_len[i], d_out_cap[i]) of its region as they were.  One
+ *     exception: mzhip_lzma_batch / mzhip_xz_batch under a d_max_out clamp below the stream's length decode the stream to
+ *     its end inside out_cap and report the clamped length.  An entry that ends with any other status may have written
+ *     anywhere inside its own out_cap;
+ *   - it READS its input in aligned 32-bit words: besides d_in + d_in_off[i] .. + d_in_len[i], the bytes of the aligned
+ *     words that hold the first and the last byte of the entry (at most 3 in front, 3 behind) must be readable.  Their
+ *     values do not matter.  (Such a word never crosses a page, so any input inside one allocation qualifies.)
  */
 #ifndef MZHIP_H
 #define MZHIP_H
@@ -80,7 +93,10 @@ MZHIP_API const char *mzhip_version(void);
  * in (the block's Huffman tables are rebuilt from there) and of the next token -- and how many bytes of history sit in
  * front of the output.  When the output buffer is full (MZHIP_STATUS_OUT_FULL: the next token does not fit) or the input
  * ends (MZHIP_STATUS_BUF_ERROR) the kernel reports such a state; the caller keeps the last 32 KiB of what it was given
- * as history, drops the input in front of the block header (and rebases the two bit positions) and calls again. */
+ * as history, drops the input in front of the block header (and rebases the two bit positions) and calls again.
+ * A stored block is one token: the room behind the history must hold it whole (65 535 bytes at most); in Huffman
+ * blocks a call makes progress whenever the next token fits the room (a match is 258 bytes at most).
+ * The out_pos bytes of history are read, never written; d_stop receives n states. */
 typedef struct mzhip_inflate_state {
     uint32_t hdr_bit; /* bit position of the current block's header, from the first input byte of the call */
     uint32_t bit;     /* bit position of the next token (== hdr_bit: at the start of the block) */

@@ -15,7 +15,8 @@
         MZ_STAT(6, 1);
         qn = 0;
         MZ_INCL_SCAN(oend, olen);
-        const uint32_t total = MZ_READLANE(oend, 63);
+        uint32_t total = MZ_READLANE(oend, 63);
+        uint32_t part_bits = 0; /* != 0: only the front of the queue fits the room; its tokens' bits */
         if (total > out_cap - out_pos) {
             /* which comes first in stream order: the token that does not fit, or a match that reaches before the
              * start of the entry (inflate checks the distance before it copies)? */
@@ -23,9 +24,27 @@
             MZ_BALLOT(over_m, P(oend) > out_cap - out_pos);
             MZ_BALLOT(far_m, P(olen) > 1u && (P(tq) >> 16) > out_pos + P(oend) - P(olen));
             const uint32_t fo = mz_ctz64(over_m);
-            status = (far_m & ((fo >= 63u) ? ~0ull : ((2ull << fo) - 1ull))) ? MZHIP_DATA_ERROR : MZHIP_OUT_FULL;
-            unwritten = 1; /* none of the queue's tokens has been written: a resumed decode starts at the queue's first (qbit) */
-            goto finish;
+            const uint32_t far_first = (far_m & ((fo >= 63u) ? ~0ull : ((2ull << fo) - 1ull))) ? 1u : 0u;
+            if (far_first || !resumable || par || fo == 0u) {
+                status = far_first ? MZHIP_DATA_ERROR : MZHIP_OUT_FULL;
+                unwritten = 1; /* none of the queue's tokens has been written: a resumed decode starts at the queue's first (qbit) */
+                goto finish;
+            }
+            /* a decode that is taken up again (include/mzhip.h: "the next token does not fit"): the fo tokens in front of
+             * the first one that does not fit are written, the state stands behind them */
+            PV(uint32_t, tb);
+            PV(uint32_t, te);
+            MZ_LANES {
+                if ((uint32_t)lane >= fo) {
+                    P(tq) = 0u;
+                    P(olen) = 0u;
+                }
+                P(tb) = P(tq) & 63u;
+            }
+            MZ_INCL_SCAN(te, tb);
+            MZ_INCL_SCAN(oend, olen);
+            part_bits = MZ_READLANE(te, 63);
+            total = MZ_READLANE(oend, 63);
         }
         uint64_t matm;
         MZ_BALLOT(matm, P(olen) > 1u);
@@ -122,4 +141,9 @@
         }
         out_pos += total;
         MZ_CRC_FOLD_SUPER_BT(crc_acc, crc_done, out + crc_base, out_pos - crc_base, crc_tab, tabs->kx4);
+        if (part_bits) {
+            bitpos = qbit + part_bits;
+            status = MZHIP_OUT_FULL;
+            goto finish;
+        }
 }

@@ -1,39 +1,162 @@
-"""Helpers for the GPU parity tests: build device-resident batches from host payloads."""
+"""Helpers for the GPU parity tests: build device-resident batches from host payloads, and -- for the bounds tests --
+lay them out between red zones over a seeded byte pattern and check afterwards that nothing outside an entry's own
+buffers and result words was written (check_guards)."""
 import importlib
 
 import numpy as np
 
 mz = importlib.import_module("minizip-ng_amd")
 
+SENTINEL = 0x5EED5EED          # pre-fill of guarded result arrays: no status, and no length any test here can produce
+RESULT_TAIL = 64               # guarded elements behind the n a result array is asked to hold
 
-def make_batch(payloads, out_caps, align=16, device="cuda:0"):
+
+def guard_pattern(nbytes, seed):
+    """Seeded, position-dependent bytes in 1 .. 255: never zero, never constant, so that a stray store of zeros, of a
+    neighbour's bytes or of the pattern of another position all show."""
+    return np.random.RandomState(seed).randint(1, 256, size=nbytes, dtype=np.uint8)
+
+
+def make_batch(payloads, out_caps, align=16, device="cuda:0", guard=0, fill=None, packed=False, odd=False):
     """payloads: list[bytes] of raw-deflate streams; out_caps: list[int].
-    -> dict of CUDA tensors laid out the way the C ABI wants them."""
+    -> dict of CUDA tensors laid out the way the C ABI wants them.
+
+    guard: red-zone bytes in front of the first entry, between entries and behind the last (input and output alike).
+    fill: seed of the byte pattern (guard_pattern) written over the WHOLE of d_out and over the gaps of d_in before the
+    launch; None = zeros, today's layout.  packed: no alignment and no red zone between entries (out_off[i + 1] ==
+    out_off[i] + out_cap[i], the layout of bench.py); the red zones stay in front and behind.  odd: every out_off odd
+    (red-zone layout only).  The dict keeps host copies of the pattern (h_fill) and of d_in (h_in)."""
     import torch
 
     n = len(payloads)
+    if packed:
+        align = 1
+    between = 0 if packed else guard
     in_len = np.array([len(p) for p in payloads], dtype=np.int64)
     in_off = np.zeros(n, dtype=np.int64)
-    pos = 0
+    pos = guard
     for i in range(n):
         in_off[i] = pos
-        pos += (int(in_len[i]) + align - 1) // align * align
-    blob = np.zeros(max(pos, 16), dtype=np.uint8)
+        pos += (int(in_len[i]) + align - 1) // align * align + between
+    pos += guard - between if n else 0
+    blob = np.zeros(max(pos, 16), dtype=np.uint8) if fill is None else guard_pattern(max(pos, 16), fill + 1)
     for i, p in enumerate(payloads):
         if p:
             blob[in_off[i]:in_off[i] + len(p)] = np.frombuffer(p, dtype=np.uint8)
     out_cap = np.array(out_caps, dtype=np.int64)
     out_off = np.zeros(n, dtype=np.int64)
-    pos = 0
+    pos = guard
     for i in range(n):
+        if odd and not packed:
+            pos |= 1
         out_off[i] = pos
-        pos += (int(out_cap[i]) + align - 1) // align * align
+        pos += (int(out_cap[i]) + align - 1) // align * align + between
+    pos += guard - between if n else 0
+    h_fill = np.zeros(max(pos, 16), dtype=np.uint8) if fill is None else guard_pattern(max(pos, 16), fill)
     dev = torch.device(device)
     return dict(
         d_in=torch.from_numpy(blob).to(dev), in_off=torch.from_numpy(in_off).to(dev),
         in_len=torch.from_numpy(in_len.astype(np.int32)).to(dev),
-        d_out=torch.zeros(max(pos, 16), dtype=torch.uint8, device=dev), out_off=torch.from_numpy(out_off).to(dev),
-        out_cap=torch.from_numpy(out_cap.astype(np.int32)).to(dev), h_out_off=out_off, n=n)
+        d_out=torch.from_numpy(h_fill.copy()).to(dev), out_off=torch.from_numpy(out_off).to(dev),
+        out_cap=torch.from_numpy(out_cap.astype(np.int32)).to(dev), h_out_off=out_off, n=n,
+        h_out_cap=out_cap, h_in_off=in_off, h_in_len=in_len, h_in=blob.copy(), h_fill=h_fill, guard=guard, packed=packed)
+
+
+def guarded_results(n, names, words=None, device="cuda:0"):
+    """{name: int32 tensor of (n + RESULT_TAIL) * words[name] elements, every one SENTINEL}.  The entry points get the base
+    pointer and are told n: elements behind n must come back untouched.  words: 32-bit words per entry (default 1; a
+    decoder state is 4, a digest 8 or 16)."""
+    import torch
+
+    words = words or {}
+    sent = np.array([SENTINEL], dtype=np.uint32).view(np.int32)[0]
+    return {k: torch.full(((n + RESULT_TAIL) * words.get(k, 1),), int(sent), dtype=torch.int32, device=torch.device(device))
+            for k in names}
+
+
+def result_words(t, n, words=1):
+    """the first n entries of a guarded result tensor -> numpy uint32 [n] or [n, words]"""
+    a = t.detach().cpu().numpy().view(np.uint32)[:n * words]
+    return a if words == 1 else a.reshape(n, words)
+
+
+def _owner(batch, j):
+    """entry whose region starts last at or in front of byte j of d_out (-1: j lies in front of the first)"""
+    return int(np.searchsorted(batch["h_out_off"], j, side="right")) - 1
+
+
+def _span_mask(size, start, end):
+    """bool[size]: True inside any [start[i], end[i]) (spans do not overlap)"""
+    d = np.zeros(size + 1, dtype=np.int64)
+    np.add.at(d, np.minimum(start, size), 1)
+    np.add.at(d, np.minimum(end, size), -1)
+    return np.cumsum(d[:size]) > 0
+
+
+def check_guards(batch, out_len, status, results=None, words=None, arbitrary=("crc", "adler", "digest"), slack_ok=False,
+                 outputs=True):
+    """What every batch entry point promises about memory it does not own (include/mzhip.h), asserted after a launch on a
+    make_batch(..., fill=seed) batch.  The message names the first offending entry and the offset in its region.
+      (a) every byte of d_out that belongs to no entry's [out_off, out_off + out_cap) still holds the pattern;
+      (b) d_in is byte-identical to what was uploaded;
+      (c) elements n .. of every guarded result array (guarded_results) still hold SENTINEL, elements 0 .. n-1 do not
+          (arrays named in `arbitrary` may hold any 32-bit value: the caller compares them with the reference);
+      (d) for entries with status == 0, bytes [out_len, out_cap) of the region still hold the pattern (slack_ok: a kernel
+          whose documented contract lets it use the whole of out_cap as scratch).
+    outputs=False: the launch has no output regions (checksums, digests): d_out must be pattern throughout.
+    -> the host copy of d_out."""
+    n = batch["n"]
+    h_out = batch["d_out"].detach().cpu().numpy()
+    fill = batch["h_fill"]
+    off, cap = batch["h_out_off"], batch["h_out_cap"]
+    changed = h_out != fill
+    if outputs and n:
+        owned = _span_mask(h_out.size, off, off + cap)
+    else:
+        owned = np.zeros(h_out.size, dtype=bool)
+    bad = np.flatnonzero(changed & ~owned)
+    if bad.size:
+        j = int(bad[0])
+        i = _owner(batch, j)
+        if i < 0:
+            raise AssertionError("(a) byte %d of d_out, %d in front of entry 0's region, was written (%d, pattern %d); %d such bytes"
+                                 % (j, int(off[0]) - j if n else 0, h_out[j], fill[j], bad.size))
+        raise AssertionError("(a) entry %d: byte at offset %d of its region (out_cap %d) was written (%d, pattern %d); next entry %s; "
+                             "%d such bytes in all" % (i, j - int(off[i]), int(cap[i]), h_out[j], fill[j],
+                                                       "%d starts at offset %d" % (i + 1, int(off[i + 1] - off[i])) if i + 1 < n else "none",
+                                                       bad.size))
+    h_in = batch["d_in"].detach().cpu().numpy()
+    bad = np.flatnonzero(h_in != batch["h_in"])
+    if bad.size:
+        j = int(bad[0])
+        i = int(np.searchsorted(batch["h_in_off"], j, side="right")) - 1
+        raise AssertionError("(b) entry %d: input byte at offset %d of its stream (in_len %d) changed from %d to %d; %d such bytes"
+                             % (i, j - int(batch["h_in_off"][i]) if i >= 0 else j, int(batch["h_in_len"][i]) if i >= 0 else 0,
+                                batch["h_in"][j], h_in[j], bad.size))
+    words = words or {}
+    for name, t in (results or {}).items():
+        w = words.get(name, 1)
+        a = t.detach().cpu().numpy().view(np.uint32)
+        tail = np.flatnonzero(a[n * w:] != SENTINEL)
+        if tail.size:
+            k = n * w + int(tail[0])
+            raise AssertionError("(c) result array %r: element %d (entry %d, n = %d) was written: 0x%08x" % (name, k, k // w, n, a[k]))
+        if name not in arbitrary:
+            un = np.flatnonzero(a[:n * w] == SENTINEL)
+            if un.size:
+                raise AssertionError("(c) result array %r: entry %d of %d was never written" % (name, int(un[0]) // w, n))
+    if outputs and n and not slack_ok:
+        ok = np.asarray(status) == 0
+        ol = np.minimum(np.asarray(out_len, dtype=np.int64), cap)
+        slack = _span_mask(h_out.size, (off + ol)[ok], (off + cap)[ok])
+        bad = np.flatnonzero(changed & slack)
+        if bad.size:
+            j = int(bad[0])
+            i = _owner(batch, j)
+            raise AssertionError("(d) entry %d (status 0, out_len %d, out_cap %d): byte at offset %d of its region, behind out_len, was "
+                                 "written (%d, pattern %d); %d such bytes in all"
+                                 % (i, int(ol[i]), int(cap[i]), j - int(off[i]), h_out[j], fill[j], bad.size))
+    return h_out
 
 
 def run_inflate(batch):

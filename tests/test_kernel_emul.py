@@ -48,16 +48,52 @@ def emu():
     return L
 
 
-def _run(fn, z, cap, *extra, mis=0, omis=0):
+RED = 256          # red-zone bytes on each side of the input and of the output handed to a core
+
+
+def _pattern(n, seed):
+    """seeded, position-dependent bytes in 1 .. 255 (never zero, never constant)"""
+    return np.random.RandomState(seed).randint(1, 256, size=n, dtype=np.uint8)
+
+
+class _Guarded:
+    """Input and output of one call of a core inside patterned buffers with red zones: the core is handed exactly in_len and
+    out_cap bytes (no slack behind either; what lies behind is pattern, not zeros).  check() asserts what include/mzhip.h
+    promises of every entry: (a) no byte outside [out, out + out_cap) is written, (b) the input is unchanged, (d) a status-0
+    call leaves [out_len, out_cap) alone (slack_ok: the LZMA / XZ decoders under a TOTAL_OUT_MAX clamp decode the stream to
+    its end inside out_cap and report the clamped length)."""
+
+    def __init__(self, z, cap, mis=0, omis=0):
+        self.n, self.cap = len(z), cap
+        self.i0, self.o0 = RED + mis, RED + omis
+        self.a = _pattern(self.i0 + len(z) + RED, 101)
+        self.a[self.i0:self.i0 + len(z)] = np.frombuffer(z, dtype=np.uint8)
+        self.a0 = self.a.copy()
+        self.out = _pattern(self.o0 + cap + RED, 102)
+        self.out0 = self.out.copy()
+        self.pin = C.cast(self.a.ctypes.data + self.i0, _u8p)
+        self.pout = C.cast(self.out.ctypes.data + self.o0, _u8p)
+
+    def check(self, st, out_len, slack_ok=False):
+        o0, cap = self.o0, self.cap
+        assert out_len <= cap, (out_len, cap)
+        bad = np.flatnonzero(self.a != self.a0)
+        assert bad.size == 0, "(b) input byte %d (in_len %d) changed" % (int(bad[0]) - self.i0, self.n)
+        for lo, hi in ((0, o0), (o0 + cap, self.out.size)):
+            bad = np.flatnonzero(self.out[lo:hi] != self.out0[lo:hi])
+            assert bad.size == 0, "(a) byte at offset %d of the output (out_cap %d, status %d) was written" % (lo + int(bad[0]) - o0, cap, st)
+        if st == 0 and not slack_ok:
+            bad = np.flatnonzero(self.out[o0 + out_len:o0 + cap] != self.out0[o0 + out_len:o0 + cap])
+            assert bad.size == 0, "(d) byte at offset %d written behind out_len %d (out_cap %d)" % (out_len + int(bad[0]), out_len, cap)
+        return self.out[o0:o0 + out_len].tobytes()
+
+
+def _run(fn, z, cap, *extra, mis=0, omis=0, slack_ok=False):
     """mis / omis: byte misalignment of the input / output pointers handed to the core (0..3)"""
-    a = np.zeros(len(z) + 8, np.uint8)
-    a[mis:mis + len(z)] = np.frombuffer(z, dtype=np.uint8)
-    out = np.zeros(cap + 8, np.uint8)
+    g = _Guarded(z, cap, mis, omis)
     ol, iu, crc = C.c_uint32(), C.c_uint32(), C.c_uint32()
-    pin = C.cast(a.ctypes.data + mis, _u8p)
-    pout = C.cast(out.ctypes.data + omis, _u8p)
-    st = fn(pin, len(z), pout, cap, *extra, C.byref(ol), C.byref(iu), C.byref(crc))
-    return st, iu.value, out[omis:omis + ol.value].tobytes(), crc.value
+    st = fn(g.pin, len(z), g.pout, cap, *extra, C.byref(ol), C.byref(iu), C.byref(crc))
+    return st, iu.value, g.check(st, ol.value, slack_ok), crc.value
 
 
 def test_lds_budget(emu):
@@ -237,7 +273,7 @@ def test_lzma_cases(emu):
                     assert st in (-3, -5), (i, len(bad), st)   # mz_stream_lzma_read maps both to MZ_DATA_ERROR
     # TOTAL_OUT_MAX clamp (mz_strm_lzma.c:214-215)
     z = _zip_lzma(c[:5000])
-    st, used, out, crc = _run(emu.emul_lzma, z, 6000, C.c_int64(3000))
+    st, used, out, crc = _run(emu.emul_lzma, z, 6000, C.c_int64(3000), slack_ok=True)
     assert st == 0 and out == c[:3000] and crc == zlib.crc32(c[:3000])
     # every lc / lp / pb liblzma accepts behind lzma_alone_decoder (mz_strm_lzma.c:126), lc + lp = 4 included
     import lzma as pylzma
@@ -459,7 +495,7 @@ def test_xz_cases_and_fuzz(emu, fixtures):
             st, used, out, crc = _run(emu.emul_xz, e["payload"], e["usize"] + 4, C.c_int64(e["usize"]))
             assert (st, used, len(out), crc) == (0, e["csize"], e["usize"], e["crc"])
     name, d, x = cases[0]
-    st, used, out, crc = _run(emu.emul_xz, x, len(d) + 64, C.c_int64(3000))
+    st, used, out, crc = _run(emu.emul_xz, x, len(d) + 64, C.c_int64(3000), slack_ok=True)
     assert st == 0 and out == d[:3000] and crc == zlib.crc32(d[:3000])
     st, used, out, crc = _run(emu.emul_xz, x, len(d) - 1, C.c_int64(-1))
     assert st == -200
@@ -493,12 +529,11 @@ def test_xz_cases_and_fuzz(emu, fixtures):
 
 
 def _deflate(emu, d, final=1):
-    a = np.frombuffer(d, dtype=np.uint8).copy() if len(d) else np.zeros(1, np.uint8)
     cap = len(d) + len(d) // 8 + 64
-    out = np.zeros(cap, np.uint8)
+    g = _Guarded(d, cap)
     ol, crc = C.c_uint32(), C.c_uint32()
-    st = emu.emul_deflate(a.ctypes.data_as(_u8p), len(d), out.ctypes.data_as(_u8p), cap, final, C.byref(ol), C.byref(crc))
-    return st, out[:ol.value].tobytes(), crc.value
+    st = emu.emul_deflate(g.pin, len(d), g.pout, cap, final, C.byref(ol), C.byref(crc))
+    return st, g.check(st, ol.value), crc.value
 
 
 def test_deflate_roundtrip(emu):
@@ -530,12 +565,11 @@ def test_deflate_roundtrip(emu):
 
 
 def _lzma_encode(emu, d, mode=0):
-    a = np.frombuffer(d, dtype=np.uint8).copy() if len(d) else np.zeros(1, np.uint8)
     cap = len(d) + len(d) // 8 + 1024
-    out = np.zeros(cap, np.uint8)
+    g = _Guarded(d, cap)
     ol, crc = C.c_uint32(), C.c_uint32()
-    st = emu.emul_lzma_encode(a.ctypes.data_as(_u8p), len(d), mode, out.ctypes.data_as(_u8p), cap, C.byref(ol), C.byref(crc))
-    return st, out[:ol.value].tobytes(), crc.value
+    st = emu.emul_lzma_encode(g.pin, len(d), mode, g.pout, cap, C.byref(ol), C.byref(crc))
+    return st, g.check(st, ol.value), crc.value
 
 
 def test_lzma_encode_long_history(emu):
@@ -1040,3 +1074,69 @@ def test_deflate_pieces_with_history(emu):
                 print("%s, %s: 16 KiB pieces with history %.4f, 64 KiB pieces without %.4f, 16 KiB without %.4f" % (
                     name, cls, len(z16) / len(data), len(z64_blind) / len(data), len(z16_blind) / len(data)))
                 assert len(z16) < len(z64_blind) < len(z16_blind)
+
+
+def test_emul_bounds_under_asan():
+    """The case list of tests/test_gpu_bounds.py through an AddressSanitizer + UBSan build of the emulation, in a child process
+    (tests/asan_bounds.py; the sanitizer runtime is preloaded into that child only): input and output are heap blocks of exactly
+    in_len (rounded up to the aligned 32-bit word the cores read in, include/mzhip.h) and out_cap bytes, so the allocation is
+    the red zone -- for over-READS too, which nothing on the device can see.  No report."""
+    import sys
+
+    out = os.path.join(ROOT, "tests", "emul", "_build")
+    os.makedirs(out, exist_ok=True)
+    so = os.path.join(out, "libemul_asan.so")
+    r = subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-Wno-unknown-pragmas",
+                        "-DMZHIP_HOST_EMUL", "-I" + os.path.join(ROOT, "minizip-ng_amd", "csrc"), "-shared", "-fPIC",
+                        os.path.join(ROOT, "tests", "emul", "emul.cpp"), "-o", so], capture_output=True, text=True)
+    if r.returncode:
+        pytest.skip("no -fsanitize=address,undefined build here: " + r.stderr[-300:])
+    rt = subprocess.run(["gcc", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
+    if not os.path.isabs(rt) or not os.path.exists(rt):
+        pytest.skip("libasan.so not found: gcc -print-file-name=libasan.so says %r" % rt)
+    env = dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "asan_bounds.py"), so], capture_output=True, text=True, env=env,
+                       timeout=3000)
+    assert r.returncode == 0 and "asan bounds replay ok" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
+    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+
+
+def test_inflate_resume_small_windows(emu):
+    """A decode taken up again (mz_inflate_state) makes progress whenever the next token fits the room behind the history:
+    streams of back-to-back 258-byte matches, text and hand-made fixed blocks window by window with 300, 4 096 and 65 536
+    bytes of room (the step loop's queue holds up to 64 tokens, 16 512 bytes: what fits of it is written, inflate_flush.inc).
+    Every window runs between red zones; the history in front is not written; the windows concatenate to zlib's bytes."""
+    from tests.test_gpu_bounds import inflate_cases
+
+    emu.emul_inflate_resume.argtypes = [_u8p, C.c_uint32, _u8p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)] + [C.POINTER(C.c_uint32)] * 3
+    c = synth.corpus()
+    room = {"random_incompressible": 65535, "max_distance": 65535, "stored_only": 65535, "stored_1000": 1000}   # a stored block is one token
+    cases = [(n, z, d) for n, z, d in inflate_cases() if len(d) <= 70000 and not n.startswith("slice")]
+    cases += [("slice0", synth.deflate_raw(c[777:777 + 8192]), c[777:777 + 8192]), ("stored_250", synth.stored_blocks(c[:3000], block=250), c[:3000])]
+    for window in (300, 4096, 65536):
+        for name, z, d in cases:
+            if room.get(name, 258) > window:
+                continue
+            got = bytearray()
+            state = (0, 0, 0, 0)
+            for rounds in range(100000):
+                hist = state[2]
+                g = _Guarded(z, hist + window, mis=rounds % 4, omis=(rounds // 4) % 4)
+                g.out[g.o0:g.o0 + hist] = np.frombuffer(bytes(got[len(got) - hist:]), dtype=np.uint8)
+                g.out0 = g.out.copy()
+                si, so = (C.c_uint32 * 4)(*state), (C.c_uint32 * 4)()
+                ol, iu, crc = C.c_uint32(), C.c_uint32(), C.c_uint32()
+                st = emu.emul_inflate_resume(g.pin, len(z), g.pout, hist + window, si, so, C.byref(ol), C.byref(iu), C.byref(crc))
+                assert st in (0, -200), (window, name, st)
+                valid = ol.value if st == 0 else so[2]
+                assert hist <= valid <= hist + window
+                new = g.check(st, valid)[hist:]
+                assert (g.out[g.o0:g.o0 + hist] == g.out0[g.o0:g.o0 + hist]).all(), (window, name, "history written")
+                assert crc.value == zlib.crc32(new), (window, name)
+                got += new
+                if st == 0:
+                    break
+                assert so[3] & 1
+                assert new or (so[0], so[1]) != state[:2], (window, name, len(got), "no progress")
+                state = (so[0], so[1], min(len(got), 32768), 1)
+            assert bytes(got) == d, (window, name)
