@@ -519,6 +519,37 @@ MZHIP_API void mzhip_prime_write_stats(uint64_t *entries, uint64_t *hits, uint64
 /* Geometry the last launch used (for reports): workgroups, waves per workgroup, LDS bytes per workgroup. */
 MZHIP_API void mzhip_inflate_launch_geometry(uint32_t n, uint32_t *grid, uint32_t *waves_per_wg, uint32_t *lds_bytes);
 
+/* Environment variables ---------------------------------------------------------------------
+ * Every MZHIP_* name the library reads (getenv in minizip-ng_amd/csrc), each read once per process unless noted.  "product" = a
+ * setting an application may rely on; "A/B" = kept to measure one path against the one it replaced; "diag" = reports or tests.
+ *
+ *   name                     default    kind     what it does
+ *   MZHIP_AUTOPRIME          512        product  0: READ streams never prime an archive on their own; <n> / <n>k: archives of up to
+ *                                                n MiB / KiB are imaged whole, larger ones rolled over window by window (read per call)
+ *   MZHIP_STREAM_WINDOW      64 MiB     product  decoded bytes per window of a READ stream in window mode (mzhip_set_stream_window)
+ *   MZHIP_STREAM_GULP        16 MiB     product  compressed bytes pulled ahead of a window's launch (mzhip_set_stream_window)
+ *   MZHIP_WRITE_SEGMENT      8 MiB      product  bytes mz_stream_lzma WRITE codes per launch (mzhip_set_write_segment)
+ *   MZHIP_STREAM_PARALLEL    1          product  0: windows are not offered to the wave-per-block decoder (mzhip_set_stream_parallel)
+ *   MZHIP_STREAM_LOOKAHEAD   1          product  0: the next window is not decoded ahead by a thread of the stream (mzhip_set_stream_lookahead)
+ *   MZHIP_WRITE_OVERLAP      1          product  0: a full WRITE segment is coded before write() returns (mzhip_set_write_overlap)
+ *   MZHIP_QUIET              unset      product  set: the first device failure under mz_crypt_crc32_update is not reported on stderr
+ *   MZHIP_AUTOPRIME_FD       1          A/B      0: rolled windows are imaged through the reader's stream only, not with pread() on the
+ *                                                archive's own descriptor (tests use it too)
+ *   MZHIP_ROLL_WINDOW_DIV    16         A/B      a rolled window is at most the budget / this (4 .. 256)
+ *   MZHIP_ROLL_BUSY          0          A/B      1: windows on their way count against the budget like live ones
+ *   MZHIP_PRIME_LARGE        1          A/B      0: DEFLATE entries of 4 MiB and more stay in the batch launch, one wave each
+ *   MZHIP_HEADER_CHECK       1          A/B      0: every candidate of the block-header search goes to the counting pass
+ *   MZHIP_CRC_LANE           2          A/B      mz_crypt_crc32_update up to 1 MiB: 2 the kernel reads the thread's page-locked block
+ *                                                over the link, 1 the block is copied to the device first, 0 pageable staging
+ *   MZHIP_POOL_STEP_MB       32         A/B      rounding step of page-locked blocks of 64 MiB and more
+ *   MZHIP_POOL_IDLE_MB       768        A/B      idle window-sized page-locked blocks kept, MiB
+ *   MZHIP_POOL_SLOTS         16         A/B      idle page-locked blocks kept, at most (1 .. 15 lower it)
+ *   MZHIP_PRIME_TRACE        unset      diag     set: timings of every prime and of the rolled windows on stderr; >= 2: every chunk too
+ *   MZHIP_PAR_TRACE          0          diag     1: seconds per step of every wave-per-block window and large entry on stderr
+ *   MZHIP_STREAM_STATS       0          diag     1: a READ stream in window mode reports its windows and times at close (read per close)
+ *   MZHIP_FAULT_INJECT       unset      diag     "crc": the next device checksum of the process fails as if the device had (tests)
+ */
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,7 @@
 // stored block the search does not see, an error, the last bits of the stream -- and the ordinary kernel goes on from that
 // block's header in stream order (the state handed back is a block header, exactly what it resumes from).
 //
-// The steps are the backend's (the device: kernel launches in mzhip_runtime.inc; the tests' host mock: loops over the
+// The steps are the backend's (the device: kernel launches in mzhip_launch.inc; the tests' host mock: loops over the
 // 64-lane emulation of the same device functions, tests/emul/mock_device.cpp); the logic between them is this file.
 #include <algorithm>
 #include <time.h>

@@ -1,6 +1,8 @@
 // mzhip_kernels.hip -- the gfx950 kernels of libmzhip.so.  The per-entry algorithms live in the *_core.h / *.inc files
-// next to this one; this file wraps them in kernels (work distribution, LDS carving) and includes the host runtime
-// (mzhip_runtime.inc: device context, launchers of the batch C ABI of include/mzhip.h, prime cache).
+// next to this one; this file wraps them in kernels (work distribution, LDS carving) and includes the launch side of the
+// runtime (mzhip_launch.inc: device context, launchers of the batch C ABI of include/mzhip.h, the host-buffer calls that
+// launch kernels themselves).  The rest of the host runtime is built apart from this translation unit (mzhip_host.cpp,
+// mzhip_crc_host.cpp, mzhip_prime.cpp); mzhip_runtime.h is the seam.
 //
 // Launch shape of K1 (MI355X: 256 CUs x 4 SIMDs, 160 KiB LDS/CU, 8 XCDs):
 //   - one wavefront per ZIP entry, 4 wavefronts per workgroup, 9.98 KiB of LDS per wave: 3.8 KiB of Huffman tables, 4.75 KiB
@@ -962,4 +964,5 @@ __global__ __launch_bounds__(256) void k_pack_pieces(PiecePackArgs a) {
     }
 }
 
-#include "mzhip_runtime.inc"
+#include "mzhip_runtime.h"
+#include "mzhip_launch.inc"

@@ -1,11 +1,14 @@
-// mzhip_runtime.inc -- the HOST runtime of libmzhip.so: device context, scratch and work-queue caches, the launchers of
-// the batch C ABI (include/mzhip.h), the synchronous host-buffer entry points the vtbl shims call, the prime cache and its
-// decode pipeline, the write-side prime.  Textually included by mzhip_kernels.hip (the launchers name the kernels and
-// their argument structs); it holds no device code.  Host side of SURVEY 8(b): what stands where the reference would call
-// zlib / liblzma one entry at a time.
+// mzhip_launch.inc -- the launch side of libmzhip.so's runtime, textually included by mzhip_kernels.hip: everything whose body
+// names a kernel, a kernel argument struct or a constant of a *_core.h.  Device context, scratch and work-queue caches, the
+// launchers of the batch C ABI (include/mzhip.h), and the host-buffer entry points that launch kernels themselves (the many-wave
+// inflate, the resumable LZMA coders, the .xz writer, the DEFLATE segment writer).  It holds no device code.  The rest of the
+// runtime -- stream pool, staging, CRC lane, gather, prime caches -- is built apart from the kernels (mzhip_host.cpp,
+// mzhip_crc_host.cpp, mzhip_prime.cpp); mzhip_runtime.h declares what crosses.
 // ---------------------------------------------------------------------------------- host
 
-namespace {
+using namespace mzh;
+
+namespace mzh {
 
 struct DeviceCtx {
     bool ready = false;
@@ -31,6 +34,9 @@ struct DeviceCtx {
     // device; 0 = not asked yet, 1 = granted, -1 = refused (the one-candidate class is used instead)
     std::atomic<int> big_lds_deflate{0}, big_lds_deflate_cost{0}, big_lds_tok{0};
 };
+} // namespace mzh
+
+namespace {
 
 // may this device run `kernel` with `bytes` of dynamic LDS per workgroup?  (asked once per device and kernel)
 bool big_lds_ok(std::atomic<int> &state, const void *kernel, size_t bytes) {
@@ -44,23 +50,14 @@ bool big_lds_ok(std::atomic<int> &state, const void *kernel, size_t bytes) {
     return st > 0;
 }
 
-constexpr int kMaxDevices = 16;
 DeviceCtx g_ctx[kMaxDevices];
 std::mutex g_mu;
-thread_local char g_err[256] = "";
 
-int32_t fail(const char *what, hipError_t e) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return -104; /* MZ_INTERNAL_ERROR */
-}
+} // namespace
 
-#define HIP_TRY(expr)                          \
-    do {                                       \
-        hipError_t _e = (expr);                \
-        if (_e != hipSuccess) return fail(#expr, _e); \
-    } while (0)
+int mzh::ctx_device(const DeviceCtx *c) { return (int)(c - g_ctx); }
 
-int32_t ctx_for_current(DeviceCtx **out) {
+int32_t mzh::ctx_for_current(DeviceCtx **out) {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= kMaxDevices) {
@@ -93,6 +90,7 @@ int32_t ctx_for_current(DeviceCtx **out) {
     return 0;
 }
 
+namespace {
 // Per-launch device scratch, stream-ordered without the runtime's memory pools.  hipMallocAsync/hipFreeAsync was the
 // first implementation; on this stack (ROCm 7.2, gfx950) the second allocation of a process intermittently came back
 // with the kernels' and copies' early writes wiped (the whole block read as zero afterwards: 16 of 100 fresh processes,
@@ -108,7 +106,9 @@ hipStream_t stream_key(hipStream_t s) {
     return s == hipStreamPerThread ? (hipStream_t)(void *)&tls_marker : s;
 }
 
-int32_t scratch_acquire(DeviceCtx *c, size_t bytes, hipStream_t s, int *slot, void **p) {
+} // namespace
+
+int32_t mzh::scratch_acquire(DeviceCtx *c, size_t bytes, hipStream_t s, int *slot, void **p) {
     std::lock_guard<std::mutex> lk(g_mu);
     constexpr int kSlots = (int)(sizeof(c->scratch) / sizeof(c->scratch[0]));
     int best = -1, empty = -1, victim = -1;
@@ -156,7 +156,7 @@ int32_t scratch_acquire(DeviceCtx *c, size_t bytes, hipStream_t s, int *slot, vo
     return 0;
 }
 
-int32_t scratch_release(DeviceCtx *c, int slot, hipStream_t s) {
+int32_t mzh::scratch_release(DeviceCtx *c, int slot, hipStream_t s) {
     std::lock_guard<std::mutex> lk(g_mu);
     DeviceCtx::ScratchEnt &e = c->scratch[slot];
     e.held = false;
@@ -166,6 +166,7 @@ int32_t scratch_release(DeviceCtx *c, int slot, hipStream_t s) {
     return 0;
 }
 
+namespace {
 // The work-queue head of one launch.  The batch entry points are asynchronous on caller-supplied streams, so a counter
 // may only be handed out again when the launch that used it last is known to be over: the next launch is on the same
 // stream (stream order puts its memset behind that kernel) or the event recorded behind it has completed.  Otherwise
@@ -232,83 +233,6 @@ uint32_t grid_for(const DeviceCtx *c, uint32_t n) {
 
 extern "C" {
 
-const char *mzhip_last_error(void) { return g_err; }
-const char *mzhip_version(void) { return "mzhip 0.6 (gfx950)"; }
-
-int32_t mzhip_device_count(void) {
-    static std::atomic<int> known{0}; /* every open() of a codec stream asks: one runtime call per process is enough */
-    if (known.load(std::memory_order_relaxed) > 0) return known.load(std::memory_order_relaxed);
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e == hipSuccess && n > 0) known.store(n);
-    if (e != hipSuccess) {
-        fail("hipGetDeviceCount", e);
-        return -1;
-    }
-    return n;
-}
-
-/* The CPUs next to a device (the NUMA node its PCIe root hangs off), from sysfs: page-locked memory that the device
- * copies from and to, and the host threads that read it, belong there -- on a two-socket box the far socket costs a
- * third of the link rate and half of the readers' memcpy rate (profiles/r3/threads_numa.log). */
-int32_t mzhip_device_local_cpus(int32_t device, char *cpulist, int32_t cap) {
-    if (!cpulist || cap < 2) return -102;
-    cpulist[0] = 0;
-    char bdf[64] = "";
-    HIP_TRY(hipDeviceGetPCIBusId(bdf, (int)sizeof(bdf), device));
-    for (char *p = bdf; *p; p++)
-        if (*p >= 'A' && *p <= 'F') *p = (char)(*p - 'A' + 'a');
-    char path[160];
-    snprintf(path, sizeof(path), "/sys/bus/pci/devices/%s/numa_node", bdf);
-    FILE *f = fopen(path, "r");
-    int node = -1;
-    if (f) {
-        if (fscanf(f, "%d", &node) != 1) node = -1;
-        fclose(f);
-    }
-    if (node < 0) return 0; /* one node, or the platform does not say */
-    snprintf(path, sizeof(path), "/sys/bus/pci/devices/%s/local_cpulist", bdf);
-    f = fopen(path, "r");
-    if (!f) return 0;
-    if (!fgets(cpulist, cap, f)) cpulist[0] = 0;
-    fclose(f);
-    size_t n = strlen(cpulist);
-    while (n && (cpulist[n - 1] == '\n' || cpulist[n - 1] == ' ')) cpulist[--n] = 0;
-    return (int32_t)n;
-}
-
-int32_t mzhip_bind_thread_near_device(int32_t device, int32_t max_cpus) {
-    char list[1024];
-    const int32_t n = mzhip_device_local_cpus(device, list, (int32_t)sizeof(list));
-    if (n <= 0) return n;
-    cpu_set_t have, want;
-    CPU_ZERO(&want);
-    if (sched_getaffinity(0, sizeof(have), &have) != 0) return 0;
-    int taken = 0;
-    for (const char *p = list; *p;) { /* "64-127,192-255": the cores first, their second hardware threads behind them */
-        char *e = nullptr;
-        long a = strtol(p, &e, 10), b = a;
-        if (e == p) break;
-        if (*e == '-') b = strtol(e + 1, &e, 10);
-        for (long c = a; c <= b && c < CPU_SETSIZE; c++)
-            if (CPU_ISSET((int)c, &have) && (max_cpus <= 0 || taken < max_cpus)) {
-                CPU_SET((int)c, &want);
-                taken++;
-            }
-        p = (*e == ',') ? e + 1 : e;
-        if (*e != ',' ) break;
-    }
-    if (!taken) return 0; /* the thread may not run on any of them: left where it is */
-    if (sched_setaffinity(0, sizeof(want), &want) != 0) return 0;
-    return taken;
-}
-
-int32_t mzhip_init(int32_t device) {
-    HIP_TRY(hipSetDevice(device));
-    DeviceCtx *c = nullptr;
-    return ctx_for_current(&c);
-}
-
 void mzhip_inflate_launch_geometry(uint32_t n, uint32_t *grid, uint32_t *waves_per_wg, uint32_t *lds_bytes) {
     DeviceCtx *c = nullptr;
     uint32_t g = 0;
@@ -329,6 +253,7 @@ int32_t mzhip_inflate_resume_batch(const void *d_in, const uint64_t *d_in_off, c
                                    const uint64_t *d_out_off, const uint32_t *d_out_cap, uint32_t n, uint32_t *d_out_len,
                                    uint32_t *d_in_used, uint32_t *d_crc, int32_t *d_status, const mzhip_inflate_state *d_resume,
                                    mzhip_inflate_state *d_stop, void *stream) {
+    static_assert(sizeof(mzhip_inflate_state) == sizeof(mz_inflate_state), "mzhip.h and inflate_core.h describe the same four words");
     if (n == 0) return 0;
     DeviceCtx *c = nullptr;
     int32_t rc = ctx_for_current(&c);
@@ -558,21 +483,6 @@ int32_t mzhip_deflate_batch(const void *d_in, const uint64_t *d_in_off, const ui
                                      d_status, stream);
 }
 
-/* How the WRITE paths (mz_stream_zlib WRITE's segments, mzhip_prime_write's entries) cut ONE stream for the device: pieces of
- * 16 KiB, a wave each, every piece but the stream's first with the 32 KiB in front of it as history (hashed, not coded:
- * mz_deflate_piece's `warm`).  Up to round 6 the pieces were 64 KiB and blind to each other: a 64 KiB entry was ONE wave's 1 024
- * dependent steps (1.8 ms at level 1; the reference's deflate: 0.5), and matches ended at every cut.  Four times the waves,
- * and the ratio is better than before (text, level 1: 0.3349 against 0.3387; 0.3548 without the history). */
-static inline uint32_t def_stream_piece(uint64_t stream_len, int32_t level) {
-    /* (the fast class on a short stream -- one 64 KiB entry through the unmodified writer -- is all latency: 8 waves instead of 4;
-     * 0.7 % more bytes than 16 KiB pieces on text, still fewer than the 64 KiB pieces of round 5) */
-    return (level >= 0 && level <= 3 && stream_len <= (256u << 10)) ? (8u << 10) : (16u << 10);
-}
-static inline uint32_t def_stream_warm(uint64_t piece_off) { return (uint32_t)(piece_off < 32768u ? piece_off : 32768u) & ~63u; }
-static int32_t deflate_batch_launch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_warm, void *d_out,
-                                    const uint64_t *d_out_off, const uint32_t *d_out_cap, const uint8_t *d_final, uint32_t n,
-                                    int32_t level, int32_t window_log2, uint32_t *d_out_len, uint32_t *d_crc, int32_t *d_status,
-                                    void *stream);
 int32_t mzhip_deflate_batch_level(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
                                   const uint64_t *d_out_off, const uint32_t *d_out_cap, const uint8_t *d_final, uint32_t n,
                                   int32_t level, int32_t window_log2, uint32_t *d_out_len, uint32_t *d_crc, int32_t *d_status,
@@ -580,10 +490,11 @@ int32_t mzhip_deflate_batch_level(const void *d_in, const uint64_t *d_in_off, co
     return deflate_batch_launch(d_in, d_in_off, d_in_len, nullptr, d_out, d_out_off, d_out_cap, d_final, n, level, window_log2, d_out_len,
                                 d_crc, d_status, stream);
 }
-static int32_t deflate_batch_launch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_warm, void *d_out,
-                                    const uint64_t *d_out_off, const uint32_t *d_out_cap, const uint8_t *d_final, uint32_t n,
-                                    int32_t level, int32_t window_log2, uint32_t *d_out_len, uint32_t *d_crc, int32_t *d_status,
-                                    void *stream) {
+} // extern "C"
+int32_t mzh::deflate_batch_launch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_warm, void *d_out,
+                                  const uint64_t *d_out_off, const uint32_t *d_out_cap, const uint8_t *d_final, uint32_t n,
+                                  int32_t level, int32_t window_log2, uint32_t *d_out_len, uint32_t *d_crc, int32_t *d_status,
+                                  void *stream) {
     if (n == 0) return 0;
     if (window_log2 < 9 || window_log2 > 15) return MZHIP_STATUS_UNSUPPORTED;
     DeviceCtx *c = nullptr;
@@ -650,7 +561,6 @@ static int32_t deflate_batch_launch(const void *d_in, const uint64_t *d_in_off, 
     return rc;
 }
 
-} // extern "C"
 namespace {
 /* K6's parse, shared by the batch, the segment and the .xz launchers: the chain pass over every stream of more than one
  * block (a.links set: `chain_waves` resident waves, one stream at a time each), then the block parse, one wave per 64 KiB
@@ -742,239 +652,6 @@ int32_t mzhip_lzma_encode_batch_preset(const void *d_in, const uint64_t *d_in_of
     rc = scratch_release(c, slot, s);
     if (le != hipSuccess) return fail("k_lzma_rc_encode_batch", le);
     return rc;
-}
-
-// ---- host-buffer conveniences (synchronous): staging through one scratch allocation per call
-
-namespace {
-struct Scratch {
-    void *p = nullptr;
-    ~Scratch() {
-        if (p) (void)hipFree(p);
-    }
-};
-// The synchronous host-buffer entry points (one entry at a time: what the vtbl shims call) run on the calling thread's
-// own stream: copies and launches are ordered on it and only that stream is waited for, so two host
-// threads never serialise on the null stream or on a device-wide synchronisation (VERDICT r2 weak 6).
-// (hipStreamPerThread itself was the first choice; with two host threads decoding entries at the same time it handed
-// back garbage result words now and then -- tests/test_gpu_dropin.py::test_archives_through_unmodified_mz_zip, one run in
-// three -- so the per-thread stream is one this library creates: a non-blocking stream per (host thread, device), made
-// on first use.)
-// A thread that exits hands its streams to a free list instead of leaking them (an application that makes a reader pool
-// per archive used to leave one stream per exited thread behind, ADVICE r3); they are recycled, never destroyed: the
-// scratch and work-queue caches remember stream identities ("the next launch is on the stream that used it last"), and a
-// recycled stream keeps the order that reasoning relies on, where a destroyed one's handle could come back as a stranger.
-struct StreamPool {
-    std::mutex mu;
-    std::vector<hipStream_t> idle[kMaxDevices];
-};
-static StreamPool *stream_pool() {
-    static StreamPool *p = new StreamPool(); // (never deleted: thread_local destructors may run after static ones)
-    return p;
-}
-struct ThreadStreams {
-    hipStream_t s[kMaxDevices] = {};
-    ~ThreadStreams() {
-        StreamPool *p = stream_pool();
-        std::lock_guard<std::mutex> g(p->mu);
-        for (int d = 0; d < kMaxDevices; d++)
-            if (s[d]) p->idle[d].push_back(s[d]);
-    }
-};
-static thread_local ThreadStreams t_streams;
-static hipStream_t mz_host_stream() {
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) return nullptr;
-    if (!t_streams.s[d]) {
-        StreamPool *p = stream_pool();
-        {
-            std::lock_guard<std::mutex> g(p->mu);
-            if (!p->idle[d].empty()) {
-                t_streams.s[d] = p->idle[d].back();
-                p->idle[d].pop_back();
-            }
-        }
-        if (!t_streams.s[d] && hipStreamCreateWithFlags(&t_streams.s[d], hipStreamNonBlocking) != hipSuccess) {
-            (void)hipGetLastError();
-            t_streams.s[d] = nullptr; /* the null stream still works, only slower */
-        }
-    }
-    return t_streams.s[d];
-}
-#define MZ_HOST_STREAM mz_host_stream()
-static inline hipError_t mz_h2d_on(hipStream_t s, void *dst, const void *src, size_t n) {
-    return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s);
-}
-static inline hipError_t mz_d2h_on(hipStream_t s, void *dst, const void *src, size_t n) {
-    const hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, s);
-    return e != hipSuccess ? e : hipStreamSynchronize(s);
-}
-static inline hipError_t mz_h2d(void *dst, const void *src, size_t n) {
-    return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, MZ_HOST_STREAM); // (pageable source: staged before the call returns)
-}
-static inline hipError_t mz_d2h(void *dst, const void *src, size_t n) {
-    const hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, MZ_HOST_STREAM);
-    return e != hipSuccess ? e : hipStreamSynchronize(MZ_HOST_STREAM);
-}
-// Staging of the synchronous host-buffer calls: a buffer of the scratch cache instead of a hipMalloc / hipFree pair
-// per call (hipFree alone is a device-wide synchronisation); released when the call returns, after its own sync.
-struct Staging {
-    DeviceCtx *c = nullptr;
-    int slot = -1;
-    void *p = nullptr;
-    int32_t get(DeviceCtx *ctx, size_t bytes) {
-        c = ctx;
-        return scratch_acquire(ctx, bytes, MZ_HOST_STREAM, &slot, &p);
-    }
-    ~Staging() {
-        if (slot >= 0) (void)scratch_release(c, slot, MZ_HOST_STREAM);
-    }
-};
-} // namespace
-
-// CRC-32 of the new bytes of a window, [hist, out_len) of the device's copy at base + out_off, in the pieces the caller will
-// hand to mz_crypt_crc32_update: the first seg_first bytes (what completes the piece the previous window left open), then
-// seg_stride at a time, the rest; one launch.  sm = device room for seg_max offsets, lengths and results.
-static int32_t window_piece_crcs(uint8_t *base, size_t out_off, uint32_t hist, uint32_t out_len, uint32_t seg_first, uint32_t seg_stride,
-                                 uint32_t *seg_crc, uint32_t seg_cap, uint32_t *nseg, uint8_t *sm, size_t seg_max) {
-    std::vector<uint64_t> off;
-    std::vector<uint32_t> len;
-    uint32_t pos = hist;
-    const uint32_t first = seg_first < out_len - hist ? seg_first : out_len - hist;
-    if (first) {
-        off.push_back(out_off + pos);
-        len.push_back(first);
-        pos += first;
-    }
-    while (pos < out_len) {
-        const uint32_t n = out_len - pos < seg_stride ? out_len - pos : seg_stride;
-        off.push_back(out_off + pos);
-        len.push_back(n);
-        pos += n;
-    }
-    const uint32_t ns = (uint32_t)len.size();
-    if (ns > seg_cap || ns > seg_max) return 0;
-    uint64_t *d_off = (uint64_t *)sm;
-    uint32_t *d_len = (uint32_t *)(sm + seg_max * 8), *d_crc = d_len + seg_max;
-    HIP_TRY(mz_h2d(d_off, off.data(), (size_t)ns * 8));
-    HIP_TRY(mz_h2d(d_len, len.data(), (size_t)ns * 4));
-    const int32_t rc = mzhip_crc32_batch(base, d_off, d_len, ns, nullptr, d_crc, MZ_HOST_STREAM);
-    if (rc) return rc;
-    HIP_TRY(mz_d2h(seg_crc, d_crc, (size_t)ns * 4));
-    if (nseg) *nseg = ns;
-    return 0;
-}
-
-// CRC-32 and / or Adler-32 of the new bytes of a window, [hist, out_len) of the device's copy at base + out_off (the wrapper
-// trailers of window mode: gzip's CRC-32, zlib's Adler-32 run over every window).  One buffer is one wave in K2 / K5, so
-// the window is cut into 64 KiB pieces -- one launch each kind -- and the pieces' checksums are combined on the host
-// (arithmetic on checksums only).  sm = device room for `room` offsets, lengths and results.
-static int32_t window_checksums(uint8_t *base, size_t out_off, uint32_t hist, uint32_t out_len, uint32_t *crc, uint32_t *adler, uint8_t *sm,
-                                size_t room, hipStream_t st = nullptr) {
-    if (!st) st = MZ_HOST_STREAM;
-    if (crc) *crc = 0u;
-    if (adler) *adler = 1u;
-    if ((!crc && !adler) || out_len <= hist) return 0;
-    std::vector<uint64_t> off;
-    std::vector<uint32_t> len;
-    for (uint32_t pos = hist; pos < out_len;) {
-        const uint32_t n = out_len - pos < 65536u ? out_len - pos : 65536u;
-        off.push_back(out_off + pos);
-        len.push_back(n);
-        pos += n;
-    }
-    const uint32_t ns = (uint32_t)len.size();
-    if (ns > room) return -104;
-    uint64_t *d_off = (uint64_t *)sm;
-    uint32_t *d_len = (uint32_t *)(sm + room * 8), *d_res = d_len + room;
-    HIP_TRY(mz_h2d_on(st, d_off, off.data(), (size_t)ns * 8));
-    HIP_TRY(mz_h2d_on(st, d_len, len.data(), (size_t)ns * 4));
-    std::vector<uint32_t> h(ns);
-    if (crc) {
-        const int32_t rc = mzhip_crc32_batch(base, d_off, d_len, ns, nullptr, d_res, st);
-        if (rc) return rc;
-        HIP_TRY(mz_d2h_on(st, h.data(), d_res, (size_t)ns * 4));
-        uint32_t v = h[0];
-        for (uint32_t i = 1; i < ns; i++) v = mzhip_crc32_combine_host(v, h[i], len[i]);
-        *crc = v;
-    }
-    if (adler) {
-        const int32_t rc = mzhip_adler32_batch(base, d_off, d_len, ns, d_res, st);
-        if (rc) return rc;
-        HIP_TRY(mz_d2h_on(st, h.data(), d_res, (size_t)ns * 4));
-        uint32_t v = h[0];
-        for (uint32_t i = 1; i < ns; i++) v = mzhip_adler32_combine_host(v, h[i], len[i]);
-        *adler = v;
-    }
-    return 0;
-}
-
-// One window of a stream that is decoded window by window (the READ shim's bounded-memory path): buf[0 .. state_in->out_pos)
-// is the history the caller kept (the last 32 KiB it was given, nothing at the start of the stream), the new bytes land
-// behind it, at most buf_cap bytes in all.  Returns the device verdict: MZHIP_OK (stream end), MZHIP_OUT_FULL (call again
-// with state_out and the tail of buf as history), MZHIP_BUF_ERROR (call again with more input from state_out's block
-// header on), or a data error.  *out_len = bytes valid in buf (history included), *crc = CRC-32 of the new bytes only.
-static int32_t inflate_window_host(const uint8_t *in, uint32_t in_len, uint8_t *buf, uint32_t buf_cap,
-                                       const mzhip_inflate_state *state_in, mzhip_inflate_state *state_out, uint32_t *out_len,
-                                       uint32_t *in_used, uint32_t *crc, uint32_t *adler, uint32_t seg_first, uint32_t seg_stride,
-                                       uint32_t *seg_crc, uint32_t seg_cap, uint32_t *nseg) {
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    const uint32_t hist = state_in ? state_in->out_pos : 0u;
-    if (hist > buf_cap) return -102; /* MZ_PARAM_ERROR */
-    // layout: [meta 128 B][in (16-aligned)][buf][segment arrays]
-    const size_t in_pad = ((size_t)in_len + 15) & ~(size_t)15;
-    const size_t buf_pad = ((size_t)buf_cap + 16 + 15) & ~(size_t)15;
-    const size_t seg_max = (seg_stride && seg_crc) ? (size_t)buf_cap / seg_stride + 3 : 0;
-    const size_t ck_max = adler ? (size_t)buf_cap / 65536u + 3 : 0;
-    const size_t total = 128 + in_pad + buf_pad + seg_max * 16 + ck_max * 16;
-    if (nseg) *nseg = 0;
-    if (adler) *adler = 1u;
-    Staging sc;
-    rc = sc.get(c, total);
-    if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
-    struct Meta {
-        uint64_t in_off, out_off;
-        uint32_t in_len, out_cap, out_len, in_used, crc;
-        int32_t status;
-        mz_inflate_state rs, st;
-    } m;
-    memset(&m, 0, sizeof(m));
-    m.in_off = 128;
-    m.out_off = 128 + in_pad;
-    m.in_len = in_len;
-    m.out_cap = buf_cap;
-    if (state_in) memcpy(&m.rs, state_in, sizeof(m.rs));
-    HIP_TRY(mz_h2d(base, &m, sizeof(m)));
-    if (in_len) HIP_TRY(mz_h2d(base + 128, in, in_len));
-    if (hist) HIP_TRY(mz_h2d(base + m.out_off, buf, hist));
-    Meta *dm = (Meta *)base;
-    rc = mzhip_inflate_resume_batch(base, &dm->in_off, &dm->in_len, base, &dm->out_off, &dm->out_cap, 1, &dm->out_len,
-                                    &dm->in_used, &dm->crc, &dm->status, (const mzhip_inflate_state *)&dm->rs,
-                                    /* no state asked for = the last call of a stream that ended short: the kernel then drops the
-                                     * resumable rules (a stored block is taken as far as it goes) -- the pointer used to be
-                                     * passed regardless, and a truncated stored stream in window mode lost its last bytes
-                                     * (found by tests/test_gpu_dropin.py::test_truncation_accounting_window_mode, round 4) */
-                                    state_out ? (mzhip_inflate_state *)&dm->st : nullptr, MZ_HOST_STREAM);
-    if (rc) return rc;
-    HIP_TRY(mz_d2h(&m, base, sizeof(m)));
-    if (m.out_len > hist) HIP_TRY(mz_d2h(buf + hist, base + m.out_off + hist, m.out_len - hist));
-    if (seg_max && m.out_len > hist) {
-        rc = window_piece_crcs(base, m.out_off, hist, m.out_len, seg_first, seg_stride, seg_crc, seg_cap, nseg, base + 128 + in_pad + buf_pad,
-                               seg_max);
-        if (rc) return rc;
-    }
-    if (adler && m.out_len > hist) {
-        rc = window_checksums(base, m.out_off, hist, m.out_len, nullptr, adler, base + 128 + in_pad + buf_pad + seg_max * 16, ck_max);
-        if (rc) return rc;
-    }
-    if (out_len) *out_len = m.out_len;
-    if (in_used) *in_used = m.in_used;
-    if (crc) *crc = m.crc;
-    if (state_out) memcpy(state_out, &m.st, sizeof(m.st));
-    return m.status;
 }
 
 } // extern "C"
@@ -1411,114 +1088,6 @@ int32_t mzhip_inflate_parallel_host(const uint8_t *in, uint32_t in_len, uint8_t 
     return 0;
 }
 
-static int32_t inflate_whole_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, uint32_t *out_len,
-                            uint32_t *in_used, uint32_t *crc, uint32_t *adler) {
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    // layout: [meta 64 B][in (16-aligned)][out]
-    const size_t in_pad = ((size_t)in_len + 15) & ~(size_t)15;
-    const size_t total = 64 + in_pad + out_cap + 16;
-    Staging sc;
-    rc = sc.get(c, total);
-    if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
-    struct Meta {
-        uint64_t in_off, out_off;
-        uint32_t in_len, out_cap, out_len, in_used, crc;
-        int32_t status;
-        uint32_t adler, pad;
-    } m;
-    memset(&m, 0, sizeof(m));
-    m.in_off = 64;
-    m.out_off = 64 + in_pad;
-    m.in_len = in_len;
-    m.out_cap = out_cap;
-    HIP_TRY(mz_h2d(base, &m, sizeof(m)));
-    if (in_len) HIP_TRY(mz_h2d(base + 64, in, in_len));
-    Meta *dm = (Meta *)base;
-    rc = mzhip_inflate_batch(base, &dm->in_off, &dm->in_len, base, &dm->out_off, &dm->out_cap, 1, &dm->out_len,
-                             &dm->in_used, &dm->crc, &dm->status, MZ_HOST_STREAM);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
-    if (adler) { /* zlib wrapper: Adler-32 of the decoded bytes, reduced on the device as well */
-        HIP_TRY(mz_d2h(&m, base, sizeof(m)));
-        rc = mzhip_adler32_batch(base, &dm->out_off, &dm->out_len, 1, &dm->adler, MZ_HOST_STREAM);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
-    }
-    HIP_TRY(mz_d2h(&m, base, sizeof(m)));
-    if (m.out_len && out) HIP_TRY(mz_d2h(out, base + m.out_off, m.out_len));
-    if (out_len) *out_len = m.out_len;
-    if (in_used) *in_used = m.in_used;
-    if (crc) *crc = m.crc;
-    if (adler) *adler = m.adler;
-    return m.status;
-}
-
-/* include/mzhip.h: one entry point for a whole entry and for one window of it.  Fields behind `size` read as zero / NULL, so a
- * caller compiled against an older (shorter) struct keeps working when fields are appended. */
-int32_t mzhip_inflate_host_a(const mzhip_inflate_host_args *ap) {
-    if (!ap || ap->size < offsetof(mzhip_inflate_host_args, buf) + sizeof(void *) || ap->size > 4096u || (ap->size & 3u)) return -102; /* MZ_PARAM_ERROR */
-    mzhip_inflate_host_args a;
-    memset(&a, 0, sizeof(a));
-    memcpy(&a, ap, ap->size < sizeof(a) ? ap->size : sizeof(a));
-    if (!a.state_in && !a.state_out) {
-        if (a.nseg) *a.nseg = 0; /* (no pieces of a whole entry: the READ shim asks the per-call CRCs of a window only) */
-        return inflate_whole_host(a.in, a.in_len, a.buf, a.buf_cap, a.out_len, a.in_used, a.crc, a.adler);
-    }
-    return inflate_window_host(a.in, a.in_len, a.buf, a.buf_cap, a.state_in, a.state_out, a.out_len, a.in_used, a.crc, a.adler,
-                               a.seg_first, a.seg_stride, a.seg_crc, a.seg_cap, a.nseg);
-}
-
-static int32_t lzma_family_host(int xz, const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, int64_t max_out,
-                                uint32_t *out_len, uint32_t *in_used, uint32_t *crc) {
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    const size_t in_pad = ((size_t)in_len + 15) & ~(size_t)15;
-    const size_t total = 64 + in_pad + out_cap + 16;
-    Staging sc;
-    rc = sc.get(c, total);
-    if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
-    struct Meta {
-        uint64_t in_off, out_off;
-        int64_t max_out;
-        uint32_t in_len, out_cap, out_len, in_used, crc;
-        int32_t status;
-    } m;
-    memset(&m, 0, sizeof(m));
-    m.in_off = 64;
-    m.out_off = 64 + in_pad;
-    m.max_out = max_out;
-    m.in_len = in_len;
-    m.out_cap = out_cap;
-    HIP_TRY(mz_h2d(base, &m, sizeof(m)));
-    if (in_len) HIP_TRY(mz_h2d(base + 64, in, in_len));
-    Meta *dm = (Meta *)base;
-    rc = lzma_family_batch(xz, base, &dm->in_off, &dm->in_len, base, &dm->out_off, &dm->out_cap, &dm->max_out, 1,
-                           &dm->out_len, &dm->in_used, &dm->crc, &dm->status, MZ_HOST_STREAM);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
-    HIP_TRY(mz_d2h(&m, base, sizeof(m)));
-    if (m.out_len && out) HIP_TRY(mz_d2h(out, base + m.out_off, m.out_len));
-    if (out_len) *out_len = m.out_len;
-    if (in_used) *in_used = m.in_used;
-    if (crc) *crc = m.crc;
-    return m.status;
-}
-
-int32_t mzhip_lzma_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, int64_t max_out,
-                        uint32_t *out_len, uint32_t *in_used, uint32_t *crc) {
-    return lzma_family_host(0, in, in_len, out, out_cap, max_out, out_len, in_used, crc);
-}
-
-int32_t mzhip_xz_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, int64_t max_out,
-                      uint32_t *out_len, uint32_t *in_used, uint32_t *crc) {
-    return lzma_family_host(1, in, in_len, out, out_cap, max_out, out_len, in_used, crc);
-}
-
 uint32_t mzhip_lzma_model_bytes(void) { return (uint32_t)(MZ_LZMA_MODEL_U16 * sizeof(uint16_t)); }
 uint32_t mzhip_lzma_encode_history_bytes(void) { return MZ_LZE_FAR_DICT; }
 
@@ -1616,48 +1185,6 @@ int32_t mzhip_lzma2_run_host(const mzhip_lzma2_run_args *ap) {
     if (m.st.flags & 1u) HIP_TRY(mz_d2h(g.model, d_model, MZ_LZMA_MODEL_U16 * sizeof(uint16_t)));
     if (g.out_len) *g.out_len = m.out_len;
     if (g.in_used) *g.in_used = m.in_used;
-    return m.status;
-}
-
-// One ZIP method-14 payload from a host buffer.
-int32_t mzhip_lzma_encode_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, uint32_t *out_len,
-                               uint32_t *crc) {
-    return mzhip_lzma_encode_host_preset(in, in_len, 1, out, out_cap, out_len, crc);
-}
-
-int32_t mzhip_lzma_encode_host_preset(const uint8_t *in, uint32_t in_len, int32_t preset, uint8_t *out, uint32_t out_cap,
-                                      uint32_t *out_len, uint32_t *crc) {
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    const size_t in_pad = ((size_t)in_len + 63) & ~(size_t)63;
-    const uint32_t cap = in_len + in_len / 8 + 1024;
-    Staging sc;
-    rc = sc.get(c, 64 + in_pad + cap);
-    if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
-    struct Meta {
-        uint64_t in_off, out_off;
-        uint32_t in_len, out_cap, out_len, crc;
-        int32_t status;
-    } m;
-    memset(&m, 0, sizeof(m));
-    m.in_off = 64;
-    m.out_off = 64 + in_pad;
-    m.in_len = in_len;
-    m.out_cap = cap;
-    HIP_TRY(mz_h2d(base, &m, sizeof(m)));
-    if (in_len) HIP_TRY(mz_h2d(base + 64, in, in_len));
-    Meta *dm = (Meta *)base;
-    rc = mzhip_lzma_encode_batch_preset(base, &dm->in_off, &dm->in_len, in_len, base, &dm->out_off, &dm->out_cap, nullptr, 1,
-                                        preset, &dm->out_len, &dm->crc, &dm->status, MZ_HOST_STREAM);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
-    HIP_TRY(mz_d2h(&m, base, sizeof(m)));
-    if (m.status == 0 && m.out_len > out_cap) m.status = MZHIP_STATUS_OUT_FULL;
-    if (m.status == 0 && m.out_len) HIP_TRY(mz_d2h(out, base + m.out_off, m.out_len));
-    if (out_len) *out_len = m.out_len;
-    if (crc) *crc = m.crc;
     return m.status;
 }
 
@@ -1945,38 +1472,6 @@ int32_t mzhip_xz_encode_block_host(const uint8_t *in, uint32_t in_len, int32_t p
     if (!in_len || !unpadded_size) return -102; /* MZ_PARAM_ERROR: a block holds at least one byte */
     return xz_encode_impl(in, in_len, preset, 1, first, out, out_cap, out_len, crc, unpadded_size);
 }
-// ... then the index over all blocks and the stream footer (host arithmetic only: a few dozen bytes)
-int32_t mzhip_xz_encode_finish_host(const uint64_t *unpadded_size, const uint64_t *uncompressed_size, uint32_t nblocks, uint8_t *out,
-                                    uint32_t out_cap, uint32_t *out_len) {
-    std::vector<uint8_t> idx;
-    auto vli = [&](uint64_t v) {
-        while (v >= 0x80) { idx.push_back((uint8_t)(v | 0x80)); v >>= 7; }
-        idx.push_back((uint8_t)v);
-    };
-    auto le32 = [](uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); };
-    idx.push_back(0x00);
-    vli(nblocks);
-    for (uint32_t i = 0; i < nblocks; i++) {
-        vli(unpadded_size[i]);
-        vli(uncompressed_size[i]);
-    }
-    while (idx.size() & 3u) idx.push_back(0);
-    uint8_t c4[4];
-    le32(c4, mzhip_crc32_host(0, idx.data(), idx.size()));
-    idx.insert(idx.end(), c4, c4 + 4);
-    uint8_t ft[12];
-    le32(ft + 4, (uint32_t)(idx.size() / 4 - 1));
-    ft[8] = 0x00;
-    ft[9] = 0x01;
-    le32(ft, mzhip_crc32_host(0, ft + 4, 6));
-    ft[10] = 'Y';
-    ft[11] = 'Z';
-    if (idx.size() + 12 > out_cap) return MZHIP_STATUS_OUT_FULL;
-    memcpy(out, idx.data(), idx.size());
-    memcpy(out + idx.size(), ft, 12);
-    if (out_len) *out_len = (uint32_t)idx.size() + 12;
-    return 0;
-}
 
 // One stream segment: split into pieces of def_stream_piece() bytes (one wave each, the 32 KiB in front as history); every piece but the
 // last ends with an empty stored block so the pieces concatenate on byte boundaries; the last piece is final iff `final`.
@@ -2096,12 +1591,8 @@ __attribute__((visibility("hidden"))) uint32_t mzhip_adler32_combine(uint32_t ad
     return mzhip_adler32_combine_host(ad1, ad2, len2);
 }
 
-// Host side of mz_crypt_crc32_update.  Buffers below MZHIP_CRC_HOST_BELOW bytes are folded right here with the
-// product's own slicing-by-4 tables (the same mzhip_crc_tables the kernels use): a launch plus two PCIe round trips for
-// a few bytes helps nobody, and the reference calls this symbol one byte at a time from mz_strm_pkcrypt.c:79,86.
-// Larger buffers go to K2 on the device.  The symbol has no error channel (mz_crypt.h:20), so a device failure neither
-// aborts the host process nor corrupts the value: the bytes are folded on the host, and the failure is latched for the
-// next codec-stream call of this thread to report (mzhip_take_crc_fault, checked by the READ / WRITE shims).
+} // extern "C"
+
 namespace {
 const mzhip_crc_tables *host_crc_tables() {
     static mzhip_crc_tables t;
@@ -2109,7 +1600,11 @@ const mzhip_crc_tables *host_crc_tables() {
     std::call_once(once, [] { mzhip_crc_tables_init(&t); });
     return &t;
 }
-uint32_t crc32_fold_host(uint32_t value, const uint8_t *p, size_t n) {
+} // namespace
+
+uint32_t mzh::crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return mzhip_crc32_combine_host(crc_a, crc_b, len_b); }
+
+uint32_t mzh::crc32_fold_host(uint32_t value, const uint8_t *p, size_t n) {
     const mzhip_crc_tables *t = host_crc_tables();
     uint32_t r = ~value; /* register inverted on entry and exit, mz_crypt.c:81,90 */
     while (n && ((uintptr_t)p & 3u)) {
@@ -2125,604 +1620,3 @@ uint32_t crc32_fold_host(uint32_t value, const uint8_t *p, size_t n) {
     while (n--) r = t->byte_tab[(r ^ *p++) & 255u] ^ (r >> 8);
     return ~r;
 }
-thread_local int32_t g_crc_fault = 0;
-std::atomic<uint64_t> g_crc_faults{0}; // process-wide, since the start (mzhip_crc_faults)
-// A device failure under mz_crypt_crc32_update: the symbol cannot fail (mz_crypt.h:20 returns the checksum), so the value comes
-// from this library's own host fold -- and the failure is made as loud as the symbol allows: mzhip_last_error() of the thread
-// names it, mzhip_crc_faults() counts it, the thread's next codec-stream call fails with MZ_STREAM_ERROR, and the first one of
-// the process says so on stderr (VERDICT r5 weak 8: "degrades silently").
-void crc_fault(const char *why) {
-    char prev[200];
-    snprintf(prev, sizeof(prev), "%s", g_err);
-    snprintf(g_err, sizeof(g_err), "mz_crypt_crc32_update: device failure (%s%s%s); the checksum was folded on the host", why, prev[0] ? ": " : "", prev);
-    g_crc_fault = -1; /* MZ_STREAM_ERROR */
-    if (g_crc_faults.fetch_add(1, std::memory_order_relaxed) == 0 && !getenv("MZHIP_QUIET"))
-        fprintf(stderr, "mzhip: %s\n", g_err);
-}
-// MZHIP_FAULT_INJECT=crc (tests): the next device checksum of the process fails as if the device had
-bool crc_fault_injected() {
-    static std::atomic<int> armed{-1};
-    int a = armed.load(std::memory_order_relaxed);
-    if (a < 0) {
-        const char *e = getenv("MZHIP_FAULT_INJECT");
-        a = (e && strcmp(e, "crc") == 0) ? 1 : 0;
-        armed.store(a, std::memory_order_relaxed);
-    }
-    if (a != 1) return false;
-    int one = 1;
-    return armed.compare_exchange_strong(one, 0);
-}
-} // namespace
-
-uint64_t mzhip_crc_faults(void) { return g_crc_faults.load(std::memory_order_relaxed); }
-
-namespace {
-// mz_crypt_crc32_update is called once per read() / write() of the zip layer (mz_zip.c:2031-2068: 64 KiB at a time from the
-// reader and writer loops of mz_zip_rw.c): what a call costs is a launch and its round trips, not the fold.  A call of up to
-// 1 MiB goes through a page-locked block of the calling thread: [256 results | 256 offsets | 256 lengths | the bytes], the
-// bytes are cut into 4 KiB pieces, a wave each, and the kernel reads them and writes its results in place over the link (no
-// copy is queued: one launch, one wait).  Before round 6 the call staged pageable memory into the scratch cache: 119 us per
-// 64 KiB (0.51 GiB/s -- 92 % of the 2.1 s a 1 GiB entry took to WRITE through the drop-in, profiles/r6/crc_calls.log).
-constexpr size_t kCrcLaneSegs = 256, kCrcLaneHead = kCrcLaneSegs * 16, kCrcLaneData = (size_t)1 << 20, kCrcLanePiece = 4096;
-struct CrcLane {
-    uint8_t *host = nullptr, *dev = nullptr; // the same block, as the host and as the device address it
-    int device = -1;
-};
-struct CrcLanePool {
-    std::mutex mu;
-    std::vector<CrcLane> idle;
-};
-CrcLanePool *crc_lane_pool() {
-    static CrcLanePool *p = new CrcLanePool(); // (never deleted: thread_local destructors may run after static ones)
-    return p;
-}
-struct ThreadCrcLane {
-    CrcLane lane;
-    ~ThreadCrcLane() {
-        if (!lane.host) return;
-        CrcLanePool *p = crc_lane_pool();
-        std::lock_guard<std::mutex> g(p->mu);
-        p->idle.push_back(lane); // (handed on to the next thread, never freed: a process has as many as it ever had threads at once)
-    }
-};
-thread_local ThreadCrcLane t_crc_lane;
-int crc_lane_mode() { // 2: the kernel reads the block over the link; 1: the block is copied to the device first; 0: the path of rounds 1 - 5
-    static const int m = [] {
-        const char *e = getenv("MZHIP_CRC_LANE");
-        return e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 2;
-    }();
-    return m;
-}
-CrcLane *crc_lane_for(int device) {
-    CrcLane &l = t_crc_lane.lane;
-    if (l.host && l.device == device) return &l;
-    if (l.host) { // (the thread moved to another device: the block it has goes back)
-        CrcLanePool *p = crc_lane_pool();
-        std::lock_guard<std::mutex> g(p->mu);
-        p->idle.push_back(l);
-        l = CrcLane();
-    }
-    {
-        CrcLanePool *p = crc_lane_pool();
-        std::lock_guard<std::mutex> g(p->mu);
-        for (size_t i = 0; i < p->idle.size(); i++)
-            if (p->idle[i].device == device) {
-                l = p->idle[i];
-                p->idle[i] = p->idle.back();
-                p->idle.pop_back();
-                return &l;
-            }
-    }
-    void *h = nullptr, *d = nullptr;
-    if (hipHostMalloc(&h, kCrcLaneHead + kCrcLaneData + 64, hipHostMallocMapped) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess || !d) {
-        (void)hipGetLastError();
-        (void)hipHostFree(h);
-        return nullptr;
-    }
-    l.host = (uint8_t *)h;
-    l.dev = (uint8_t *)d;
-    l.device = device;
-    return &l;
-}
-// -> 0 and *out, or non-zero: the caller takes the general path
-int crc32_lane(DeviceCtx *c, uint32_t value, const uint8_t *buf, size_t size, uint32_t *out) {
-    const int mode = crc_lane_mode();
-    if (mode == 0 || size > kCrcLaneData) return 1;
-    CrcLane *l = crc_lane_for((int)(c - g_ctx));
-    if (!l) return 1;
-    uint32_t *h_crc = (uint32_t *)l->host;
-    uint64_t *h_off = (uint64_t *)(l->host + kCrcLaneSegs * 4);
-    uint32_t *h_len = (uint32_t *)(l->host + kCrcLaneSegs * 12);
-    const uint32_t nseg = (uint32_t)((size + kCrcLanePiece - 1) / kCrcLanePiece);
-    for (uint32_t i = 0; i < nseg; i++) {
-        h_off[i] = kCrcLaneHead + (uint64_t)i * kCrcLanePiece;
-        const size_t left = size - (size_t)i * kCrcLanePiece;
-        h_len[i] = (uint32_t)(left < kCrcLanePiece ? left : kCrcLanePiece);
-    }
-    memcpy(l->host + kCrcLaneHead, buf, size);
-    hipStream_t s = MZ_HOST_STREAM;
-    if (mode == 2) {
-        if (mzhip_crc32_batch(l->dev, (const uint64_t *)(l->dev + kCrcLaneSegs * 4), (const uint32_t *)(l->dev + kCrcLaneSegs * 12), nseg, nullptr,
-                              (uint32_t *)l->dev, s) != 0)
-            return 2;
-        if (hipStreamSynchronize(s) != hipSuccess) return 2;
-    } else {
-        Staging sc;
-        if (sc.get(c, kCrcLaneHead + size) != 0) return 2;
-        uint8_t *base = (uint8_t *)sc.p;
-        if (hipMemcpyAsync(base + kCrcLaneSegs * 4, l->host + kCrcLaneSegs * 4, kCrcLaneHead - kCrcLaneSegs * 4 + size, hipMemcpyHostToDevice, s) != hipSuccess) return 2;
-        if (mzhip_crc32_batch(base, (const uint64_t *)(base + kCrcLaneSegs * 4), (const uint32_t *)(base + kCrcLaneSegs * 12), nseg, nullptr, (uint32_t *)base, s) != 0)
-            return 2;
-        if (hipMemcpyAsync(h_crc, base, (size_t)nseg * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return 2;
-        if (hipStreamSynchronize(s) != hipSuccess) return 2;
-    }
-    uint32_t v = value;
-    for (uint32_t i = 0; i < nseg; i++) v = mzhip_crc32_combine_host(v, h_crc[i], h_len[i]);
-    *out = v;
-    return 0;
-}
-} // namespace
-
-uint32_t mzhip_crc32_host(uint32_t value, const uint8_t *buf, size_t size) {
-    if (size == 0) return value;
-    if (size < MZHIP_CRC_HOST_BELOW) return crc32_fold_host(value, buf, size);
-    DeviceCtx *c = nullptr;
-    if (ctx_for_current(&c)) {
-        crc_fault("no usable HIP device");
-        return crc32_fold_host(value, buf, size);
-    }
-    if (size <= kCrcLaneData && crc_lane_mode() != 0) {
-        if (crc_fault_injected()) {
-            crc_fault("staging, copy or launch failed");
-            return crc32_fold_host(value, buf, size);
-        }
-        uint32_t v = 0;
-        const int lr = crc32_lane(c, value, buf, size, &v);
-        if (lr == 0) return v;
-        if (lr == 2) {
-            (void)hipGetLastError();
-            crc_fault("launch or wait failed");
-            return crc32_fold_host(value, buf, size);
-        }
-        /* (no page-locked block to be had: the general path below) */
-    }
-    // segments of 256 KiB, one wave each; segment CRCs are chained with x^(8*len) shifts
-    // (32-bit arithmetic on checksums only, no byte is touched on the host).
-    const uint32_t seg = 256u << 10;
-    const uint32_t nseg = (uint32_t)((size + seg - 1) / seg);
-    const size_t meta = (size_t)nseg * (8 + 4 + 4);
-    const size_t meta_pad = (meta + 63) & ~(size_t)63;
-    Staging sc;
-    uint64_t *h_off = (uint64_t *)malloc(meta_pad);
-    bool ok = h_off != nullptr && sc.get(c, meta_pad + size) == 0 && !crc_fault_injected();
-    uint32_t v = value;
-    if (ok) {
-        uint8_t *base = (uint8_t *)sc.p;
-        uint32_t *h_len = (uint32_t *)(h_off + nseg);
-        uint32_t *h_crc = h_len + nseg;
-        for (uint32_t i = 0; i < nseg; i++) {
-            h_off[i] = meta_pad + (uint64_t)i * seg;
-            size_t left = size - (size_t)i * seg;
-            h_len[i] = (uint32_t)(left < seg ? left : seg);
-        }
-        ok = mz_h2d(base, h_off, meta) == hipSuccess &&
-             mz_h2d(base + meta_pad, buf, size) == hipSuccess;
-        uint64_t *d_off = (uint64_t *)base;
-        uint32_t *d_len = (uint32_t *)(d_off + nseg);
-        uint32_t *d_crc = d_len + nseg;
-        ok = ok && mzhip_crc32_batch(base, d_off, d_len, nseg, nullptr, d_crc, MZ_HOST_STREAM) == 0;
-        ok = ok && mz_d2h(h_crc, d_crc, nseg * sizeof(uint32_t)) == hipSuccess;
-        if (ok)
-            for (uint32_t i = 0; i < nseg; i++) v = mzhip_crc32_combine_host(v, h_crc[i], h_len[i]);
-    }
-    free(h_off);
-    if (!ok) {
-        crc_fault("staging, copy or launch failed");
-        return crc32_fold_host(value, buf, size);
-    }
-    return v;
-}
-
-// a thread the shims start for a stream (shim_zlib.c: the window decoded ahead) works on the device of the thread that owns the stream
-__attribute__((visibility("hidden"))) void mzhip_thread_use_device(int32_t dev) {
-    if (dev >= 0) (void)hipSetDevice(dev);
-}
-
-// the failure a mz_crypt_crc32_update of this thread could not report (0 = none); reading clears it
-__attribute__((visibility("hidden"))) int32_t mzhip_take_crc_fault(void) {
-    const int32_t f = g_crc_fault;
-    g_crc_fault = 0;
-    return f;
-}
-
-} // extern "C"
-
-extern "C" {
-
-/* The per-archive result gather behind the C ABI (SURVEY 8e; north_star: "RCCL over xGMI only for the final per-archive CRC
- * gather").  libmzhip.so does not link RCCL: the library is opened with dlopen() when the first call with a communicator needs
- * it, so a single-GPU application never loads it. */
-namespace {
-typedef int (*nccl_allgather_fn)(const void *, void *, size_t, int, void *, hipStream_t);
-nccl_allgather_fn g_nccl_allgather = nullptr;
-std::once_flag g_nccl_once;
-void nccl_load() {
-    for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1", "/opt/rocm/lib/librccl.so"}) {
-        void *h = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-        if (h) {
-            g_nccl_allgather = (nccl_allgather_fn)dlsym(h, "ncclAllGather");
-            if (g_nccl_allgather) return;
-        }
-    }
-}
-} // namespace
-
-int32_t mzhip_gather_results(void *comm, int32_t rank, int32_t world, const int64_t *bounds, const uint32_t *d_crc, const int32_t *d_status,
-                             uint32_t *d_crc_all, int32_t *d_status_all, void *stream) {
-    if (world < 1 || rank < 0 || rank >= world || !bounds || !d_crc_all || !d_status_all) return -102; /* MZ_PARAM_ERROR */
-    hipStream_t s = (hipStream_t)stream;
-    /* every rank's slice, not only this one's: a table that runs backwards anywhere would turn into a huge copy count below */
-    if (bounds[0] < 0) return -102;
-    for (int32_t r = 0; r < world; r++)
-        if (bounds[r + 1] < bounds[r] || bounds[r + 1] - bounds[r] > (int64_t)0x3FFFFFFF) return -102;
-    const int64_t n_local = bounds[rank + 1] - bounds[rank];
-    if (n_local > 0 && (!d_crc || !d_status)) return -102;
-    if (world == 1 || !comm) {
-        if (world != 1) return -102; /* several ranks need the job's communicator */
-        if (n_local) {
-            HIP_TRY(hipMemcpyAsync(d_crc_all + bounds[0], d_crc, (size_t)n_local * 4, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipMemcpyAsync(d_status_all + bounds[0], d_status, (size_t)n_local * 4, hipMemcpyDeviceToDevice, s));
-        }
-        return 0;
-    }
-    std::call_once(g_nccl_once, nccl_load);
-    if (!g_nccl_allgather) {
-        snprintf(g_err, sizeof(g_err), "mzhip_gather_results: librccl.so could not be loaded (dlopen)");
-        return -109; /* MZ_SUPPORT_ERROR */
-    }
-    int64_t mx = 0;
-    for (int32_t r = 0; r < world; r++) mx = std::max(mx, bounds[r + 1] - bounds[r]);
-    if (mx == 0) return 0;
-    /* ncclAllGather moves equal blocks: every rank sends {crc[0 .. mx), status[0 .. mx)} (its slice, padded), one collective; the
-     * slices are then copied to where the table wants them.  The block buffers come from the scratch cache of the device. */
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    int slot = -1;
-    void *p = nullptr;
-    rc = scratch_acquire(c, (size_t)(world + 1) * 2 * (size_t)mx * 4, s, &slot, &p);
-    if (rc) return rc;
-    uint32_t *send = (uint32_t *)p, *recv = send + 2 * mx;
-    hipError_t e = hipSuccess;
-    if (n_local) {
-        e = hipMemcpyAsync(send, d_crc, (size_t)n_local * 4, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(send + mx, d_status, (size_t)n_local * 4, hipMemcpyDeviceToDevice, s);
-    }
-    int nr = 0;
-    if (e == hipSuccess) nr = g_nccl_allgather(send, recv, (size_t)(2 * mx), 2 /* ncclInt32 */, comm, s);
-    for (int32_t r = 0; e == hipSuccess && nr == 0 && r < world; r++) {
-        const int64_t cnt = bounds[r + 1] - bounds[r];
-        if (!cnt) continue;
-        e = hipMemcpyAsync(d_crc_all + bounds[r], recv + (size_t)r * 2 * mx, (size_t)cnt * 4, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_status_all + bounds[r], recv + (size_t)r * 2 * mx + mx, (size_t)cnt * 4, hipMemcpyDeviceToDevice, s);
-    }
-    (void)scratch_release(c, slot, s);
-    if (e != hipSuccess) return fail("mzhip_gather_results", e);
-    if (nr != 0) {
-        snprintf(g_err, sizeof(g_err), "mzhip_gather_results: ncclAllGather returned %d", nr);
-        return -104; /* MZ_INTERNAL_ERROR */
-    }
-    return 0;
-}
-
-} // extern "C"
-
-#include "mzhip_prime.inc"
-
-
-// ---------------------------------------------------------------------------------------------------------
-// Write-side prime (SURVEY 8b "Batching", config 5): compress many buffers in ONE launch per group ahead of the
-// reference's untouched writer loop (mz_zip_writer_add_buffer -> mz_zip_entry_write -> mz_stream_zlib_write ->
-// mz_crypt_crc32_update, one entry at a time).  The codec stream's WRITE side follows the bytes it is handed against
-// the primed buffers (exact comparison, chunk by chunk); when an entry turns out to be one of them, close() emits the
-// cached stream instead of launching, and the CRC updates of the 65 535-byte writer chunks (mz_zip_rw.c:55) are
-// answered from device-computed segment CRCs.  Anything that diverges from the primed bytes falls back to the
-// ordinary path with nothing lost.  The caller keeps the primed buffers alive and unchanged until the clear.
-
-namespace {
-struct WPrimed {
-    const uint8_t *src;
-    uint32_t len, out_len, crc;
-    uint64_t out_off;
-    int64_t seg0;
-};
-struct WPrimeCache {
-    std::vector<WPrimed> ents;
-    std::unordered_multimap<uint64_t, uint32_t> by_key;
-    std::vector<uint32_t> seg_crc;
-    std::vector<uint8_t *> outs; // one host buffer per launch group
-    uint64_t hits = 0, misses = 0;
-};
-WPrimeCache g_wprime[3]; // methods 8, 14 (95 not primed: its container is laid out per entry on the host)
-std::mutex g_wprime_mu;
-
-int wprime_slot(int32_t method) { return method == 8 ? 0 : method == 14 ? 1 : -1; }
-
-// key of an entry's first writer chunk: its length and its first and last 16 bytes
-uint64_t wprime_key(const uint8_t *p, uint32_t n) {
-    uint64_t a = 0, b = 0, c = 0, d = 0;
-    memcpy(&a, p, 8);
-    memcpy(&b, p + 8, 8);
-    memcpy(&c, p + n - 16, 8);
-    memcpy(&d, p + n - 8, 8);
-    uint64_t h = 0x9E3779B97F4A7C15ull ^ n;
-    h = (h ^ a) * 0xFF51AFD7ED558CCDull;
-    h = (h ^ (h >> 32) ^ b) * 0xC4CEB9FE1A85EC53ull;
-    h = (h ^ (h >> 29) ^ c) * 0xFF51AFD7ED558CCDull;
-    h = (h ^ (h >> 32) ^ d) * 0xC4CEB9FE1A85EC53ull;
-    return h ^ (h >> 31);
-}
-
-void wprime_clear_locked(WPrimeCache &w) {
-    for (uint8_t *p : w.outs) free(p);
-    w = WPrimeCache();
-}
-} // namespace
-
-extern "C" {
-
-void mzhip_prime_write_clear(void) {
-    std::lock_guard<std::mutex> lk(g_wprime_mu);
-    for (WPrimeCache &w : g_wprime) wprime_clear_locked(w);
-}
-
-void mzhip_prime_write_stats(uint64_t *entries, uint64_t *hits, uint64_t *misses) {
-    std::lock_guard<std::mutex> lk(g_wprime_mu);
-    uint64_t e = 0, h = 0, m = 0;
-    for (const WPrimeCache &w : g_wprime) {
-        e += w.ents.size();
-        h += w.hits;
-        m += w.misses;
-    }
-    if (entries) *entries = e;
-    if (hits) *hits = h;
-    if (misses) *misses = m;
-}
-
-int64_t mzhip_prime_write(int32_t method, const uint8_t *blob, const uint64_t *off, const uint32_t *len, uint32_t n) {
-    const int slot = wprime_slot(method);
-    if (slot < 0 || (!blob && n) || (n && (!off || !len))) return -102; /* MZ_PARAM_ERROR */
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    const uint32_t kMaxLen = 8u << 20; /* what the WRITE shims hold before their first launch */
-    const uint32_t blk64 = 64u << 10; /* (method 14: blocks of the parse) */
-    WPrimeCache fresh;
-    // launch groups: bounded input bytes and bounded token scratch
-    std::vector<uint32_t> ids;
-    for (uint32_t i = 0; i < n; i++)
-        if (len[i] >= 16u && len[i] <= kMaxLen) ids.push_back(i);
-    size_t g0 = 0;
-    while (g0 < ids.size()) {
-        size_t g1 = g0;
-        uint64_t in_bytes = 0, units = 0;
-        uint32_t maxlen = 0;
-        while (g1 < ids.size()) {
-            const uint32_t l = len[ids[g1]];
-            const uint32_t ml = l > maxlen ? l : maxlen;
-            const uint64_t u = method == 8 ? units + (l + (8u << 10) - 1) / (8u << 10)
-                                           : (uint64_t)(g1 - g0 + 1) * ((ml + blk64 - 1) / blk64);
-            if (g1 > g0 && (in_bytes + l > ((uint64_t)1 << 30) || u > 32768u)) break;
-            in_bytes += (l + 63u) & ~63u;
-            units = u;
-            maxlen = ml;
-            g1++;
-        }
-        const uint32_t gn = (uint32_t)(g1 - g0);
-        // descriptors: method 8 = one per piece (the cut of deflate_segment_host at level 1: the archive is the same either way), method 14 = one per entry
-        std::vector<uint64_t> in_off, out_off, seg_off;
-        std::vector<uint32_t> in_len, out_cap, seg_len, first_unit(gn + 1), warm;
-        std::vector<uint8_t> fin;
-        uint64_t ipos = 0, opos = 0;
-        std::vector<uint64_t> ent_in(gn);
-        for (uint32_t e = 0; e < gn; e++) {
-            const uint32_t l = len[ids[g0 + e]];
-            ent_in[e] = ipos;
-            first_unit[e] = (uint32_t)in_off.size();
-            if (method == 8) {
-                const uint32_t piece = def_stream_piece(l, 1), pcap = piece + piece / 8 + 64;
-                for (uint32_t o = 0; o < l; o += piece) {
-                    in_off.push_back(ipos + o);
-                    in_len.push_back(l - o < piece ? l - o : piece);
-                    warm.push_back(def_stream_warm(o));
-                    out_off.push_back(opos);
-                    out_cap.push_back(pcap);
-                    fin.push_back(o + piece >= l ? 1 : 0);
-                    opos += pcap;
-                }
-            } else {
-                const uint32_t cap = l + l / 8 + 1024;
-                in_off.push_back(ipos);
-                in_len.push_back(l);
-                out_off.push_back(opos);
-                out_cap.push_back(cap);
-                opos += (cap + 63u) & ~63u;
-            }
-            for (uint32_t o = 0; o < l; o += kSeg) {
-                seg_off.push_back(ipos + o);
-                seg_len.push_back(l - o < kSeg ? l - o : kSeg);
-            }
-            ipos += (l + 63u) & ~63u;
-        }
-        first_unit[gn] = (uint32_t)in_off.size();
-        const uint32_t nu = (uint32_t)in_off.size(), ns = (uint32_t)seg_off.size();
-        const uint64_t out_base = ipos; /* outputs behind the inputs in one allocation */
-        for (uint64_t &o : out_off) o += out_base;
-        const size_t meta = (size_t)nu * (8 + 8 + 4 + 4 + 4 + 4 + 4 + 4 + 1) + (size_t)ns * (8 + 4 + 4) + 256;
-        Scratch d_data, d_meta;
-        HIP_TRY(hipMalloc(&d_data.p, out_base + opos + 64));
-        HIP_TRY(hipMalloc(&d_meta.p, meta));
-        {   /* the group's inputs in their padded device layout, one transfer */
-            uint8_t *stage = (uint8_t *)malloc(ipos + 64);
-            if (!stage) return -4;
-            for (uint32_t e = 0; e < gn; e++) memcpy(stage + ent_in[e], blob + off[ids[g0 + e]], len[ids[g0 + e]]);
-            const hipError_t ce = hipMemcpy(d_data.p, stage, ipos, hipMemcpyHostToDevice);
-            free(stage);
-            if (ce != hipSuccess) return fail("hipMemcpy (buffers to prime)", ce);
-        }
-        uint8_t *m = (uint8_t *)d_meta.p;
-        uint64_t *d_in_off = (uint64_t *)m, *d_out_off = d_in_off + nu, *d_seg_off = d_out_off + nu;
-        uint32_t *d_in_len = (uint32_t *)(d_seg_off + ns), *d_out_cap = d_in_len + nu, *d_out_len = d_out_cap + nu,
-                 *d_crc = d_out_len + nu;
-        int32_t *d_status = (int32_t *)(d_crc + nu);
-        uint32_t *d_seg_len = (uint32_t *)(d_status + nu), *d_seg_crc = d_seg_len + ns;
-        uint32_t *d_warm = d_seg_crc + ns;
-        uint8_t *d_fin = (uint8_t *)(d_warm + nu);
-        HIP_TRY(hipMemcpy(d_in_off, in_off.data(), (size_t)nu * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_out_off, out_off.data(), (size_t)nu * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_in_len, in_len.data(), (size_t)nu * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_out_cap, out_cap.data(), (size_t)nu * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_seg_off, seg_off.data(), (size_t)ns * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_seg_len, seg_len.data(), (size_t)ns * 4, hipMemcpyHostToDevice));
-        if (method == 8) {
-            HIP_TRY(hipMemcpy(d_fin, fin.data(), nu, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d_warm, warm.data(), (size_t)nu * 4, hipMemcpyHostToDevice));
-            rc = deflate_batch_launch(d_data.p, d_in_off, d_in_len, d_warm, d_data.p, d_out_off, d_out_cap, d_fin, nu, 1, 15, d_out_len, d_crc,
-                                      d_status, nullptr);
-        } else {
-            rc = mzhip_lzma_encode_batch(d_data.p, d_in_off, d_in_len, maxlen, d_data.p, d_out_off, d_out_cap, nullptr, nu,
-                                         d_out_len, d_crc, d_status, nullptr);
-        }
-        if (rc) return rc;
-        rc = mzhip_crc32_batch(d_data.p, d_seg_off, d_seg_len, ns, nullptr, d_seg_crc, nullptr);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(nullptr)); /* the launches above are on the null stream */
-        std::vector<uint32_t> h_len(nu), h_crc(nu), h_seg(ns);
-        std::vector<int32_t> h_st(nu);
-        HIP_TRY(hipMemcpy(h_len.data(), d_out_len, (size_t)nu * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(h_crc.data(), d_crc, (size_t)nu * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(h_st.data(), d_status, (size_t)nu * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(h_seg.data(), d_seg_crc, (size_t)ns * 4, hipMemcpyDeviceToHost));
-        // one transfer of the whole output region, then the pieces are closed up on the host
-        uint8_t *raw = (uint8_t *)malloc(opos + 64);
-        if (!raw) return -4;
-        hipError_t he = hipMemcpy(raw, (uint8_t *)d_data.p + out_base, opos, hipMemcpyDeviceToHost);
-        if (he != hipSuccess) {
-            free(raw);
-            return fail("hipMemcpy (primed streams)", he);
-        }
-        uint64_t packed = 0;
-        for (uint32_t u = 0; u < nu; u++) packed += h_len[u];
-        uint8_t *host_out = (uint8_t *)malloc(packed + 64);
-        if (!host_out) {
-            free(raw);
-            return -4;
-        }
-        uint64_t w = 0;
-        int64_t seg_at = (int64_t)fresh.seg_crc.size(), seg_i = 0;
-        for (uint32_t e = 0; e < gn; e++) {
-            const uint32_t i = ids[g0 + e], l = len[i];
-            const uint32_t nseg = (l + kSeg - 1) / kSeg;
-            bool ok = true;
-            uint32_t crc = 0;
-            const uint64_t w0 = w;
-            for (uint32_t u = first_unit[e]; u < first_unit[e + 1]; u++) {
-                if (h_st[u] != 0 || h_len[u] > out_cap[u]) ok = false;
-                if (!ok) break;
-                memcpy(host_out + w, raw + (out_off[u] - out_base), h_len[u]);
-                w += h_len[u];
-                crc = (u == first_unit[e]) ? h_crc[u] : mzhip_crc32_combine_host(crc, h_crc[u], in_len[u]);
-            }
-            if (ok) {
-                WPrimed pe;
-                pe.src = blob + off[i];
-                pe.len = l;
-                pe.out_off = w0;
-                pe.out_len = (uint32_t)(w - w0);
-                pe.crc = crc;
-                pe.seg0 = seg_at + seg_i;
-                // out_off is relative to this group's buffer: remember which one through the pointer table
-                pe.out_off |= (uint64_t)fresh.outs.size() << 48;
-                fresh.by_key.emplace(wprime_key(pe.src, l < kSeg ? l : kSeg), (uint32_t)fresh.ents.size());
-                fresh.ents.push_back(pe);
-            } else {
-                w = w0; /* not cached: the ordinary path and its exact behaviour */
-            }
-            seg_i += nseg;
-        }
-        fresh.seg_crc.insert(fresh.seg_crc.end(), h_seg.begin(), h_seg.end());
-        fresh.outs.push_back(host_out);
-        free(raw);
-        g0 = g1;
-    }
-    std::lock_guard<std::mutex> lk(g_wprime_mu);
-    wprime_clear_locked(g_wprime[slot]);
-    g_wprime[slot] = std::move(fresh);
-    return (int64_t)g_wprime[slot].ents.size();
-}
-
-// Used by the WRITE shims.  *id < 0: does a primed buffer start with these `size` bytes?  *id >= 0: do the bytes at
-// `pos` of that buffer continue with them?  Returns 1 on a match; *have_crc says whether the chunk is one of the
-// buffer's 65 535-byte segments, whose CRC-32 the device already computed.
-__attribute__((visibility("hidden"))) int32_t mzhip_wprime_track(int32_t method, int64_t *id, int64_t pos, const uint8_t *buf,
-                                                                 int32_t size, uint32_t *chunk_crc, int32_t *have_crc,
-                                                                 const uint8_t **src) {
-    const int slot = wprime_slot(method);
-    *have_crc = 0;
-    if (slot < 0 || size <= 0) return 0;
-    std::lock_guard<std::mutex> lk(g_wprime_mu);
-    WPrimeCache &w = g_wprime[slot];
-    if (w.ents.empty()) return 0;
-    const WPrimed *e = nullptr;
-    if (*id < 0) {
-        if (pos != 0 || size < 16) return 0;
-        auto range = w.by_key.equal_range(wprime_key(buf, (uint32_t)size));
-        for (auto it = range.first; it != range.second; ++it) {
-            const WPrimed &c = w.ents[it->second];
-            const uint32_t first = c.len < kSeg ? c.len : kSeg;
-            if (first == (uint32_t)size && memcmp(c.src, buf, (size_t)size) == 0) {
-                *id = (int64_t)it->second;
-                e = &c;
-                break;
-            }
-        }
-        if (!e) {
-            w.misses++;
-            return 0;
-        }
-    } else {
-        if ((uint64_t)*id >= w.ents.size()) return 0;
-        e = &w.ents[(size_t)*id];
-        if (pos + size > (int64_t)e->len || memcmp(e->src + pos, buf, (size_t)size) != 0) return 0;
-    }
-    if (pos % kSeg == 0 && ((uint32_t)size == kSeg || pos + size == (int64_t)e->len)) {
-        *chunk_crc = w.seg_crc[(size_t)(e->seg0 + pos / kSeg)];
-        *have_crc = 1;
-        *src = e->src + pos; /* the primed bytes these were compared with: what the CRC symbol compares again */
-    }
-    return 1;
-}
-
-// The primed buffer behind `id`: its bytes (for a stream that diverged and must fall back), and -- when the entry
-// ended exactly at the buffer's end (pos == len) -- the cached stream.  Returns 1 if the stream may be emitted.
-__attribute__((visibility("hidden"))) int32_t mzhip_wprime_result(int32_t method, int64_t id, int64_t pos, const uint8_t **src,
-                                                                  const uint8_t **out, uint32_t *out_len) {
-    const int slot = wprime_slot(method);
-    if (slot < 0) return 0;
-    std::lock_guard<std::mutex> lk(g_wprime_mu);
-    WPrimeCache &w = g_wprime[slot];
-    if (id < 0 || (uint64_t)id >= w.ents.size()) return 0;
-    const WPrimed &e = w.ents[(size_t)id];
-    *src = e.src;
-    if (pos != (int64_t)e.len) return 0;
-    *out = w.outs[(size_t)(e.out_off >> 48)] + (e.out_off & (((uint64_t)1 << 48) - 1));
-    *out_len = e.out_len;
-    w.hits++;
-    return 1;
-}
-
-} // extern "C"

@@ -1,6 +1,7 @@
 // mzhip_prime.inc -- the READ-side prime cache of libmzhip.so and its decode pipeline (host code, no device code).
-// Textually included by mzhip_runtime.inc (which supplies DeviceCtx / ctx_for_current, HIP_TRY / fail / g_err, Scratch, the batch
-// launchers and mzhip_shard_bounds) -- and, as TEST INFRASTRUCTURE, by tests/emul/mock_device.cpp, which supplies the same names over
+// Textually included by mzhip_prime.cpp (which supplies DeviceCtx / ctx_for_current, HIP_TRY / fail / g_err through mzhip_runtime.h,
+// Scratch, lzma_family_batch, mzhip_crc32_combine_host and the batch launchers of include/mzhip.h) -- and, as TEST INFRASTRUCTURE, by
+// tests/emul/mock_device.cpp, which supplies the same names over
 // a synchronous stand-in for the HIP runtime and the host emulation of the device cores, so that the cache, the pipeline and
 // shim_autoprime.c run behind the unmodified zip layer in a container without a GPU (also under the sanitizers).
 

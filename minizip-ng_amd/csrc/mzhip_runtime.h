@@ -1,0 +1,103 @@
+// mzhip_runtime.h -- the seam between the two halves of libmzhip.so's C++ runtime.  PRIVATE: not part of the ABI, every
+// name here has hidden visibility.
+//   device TU  mzhip_kernels.hip + mzhip_launch.inc (hipcc): the kernels and every function whose body names a kernel, a
+//              kernel argument struct or a constant of a core header -- device context, scratch and work-queue caches, launchers;
+//   host TUs   mzhip_host.cpp, mzhip_crc_host.cpp, mzhip_prime.cpp (the host C++ compiler, <hip/hip_runtime_api.h> only):
+//              device queries, the per-thread stream pool, staging, the one-entry host calls that only call launchers, the
+//              CRC lane, the RCCL gather, both prime caches.
+// This header declares exactly what crosses between them and names no kernel and no core type.
+#ifndef MZHIP_RUNTIME_H
+#define MZHIP_RUNTIME_H
+
+#include <hip/hip_runtime_api.h>
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/mzhip.h"
+
+namespace mzh {
+
+// ---- defined in mzhip_host.cpp
+extern __thread char g_err[256]; // the text behind mzhip_last_error(), per thread
+int32_t fail(const char *what, hipError_t e);
+#define HIP_TRY(expr)                               \
+    do {                                            \
+        hipError_t _e = (expr);                     \
+        if (_e != hipSuccess) return mzh::fail(#expr, _e); \
+    } while (0)
+
+// the calling thread's own non-blocking stream on the current device (made on first use, recycled when the thread exits)
+hipStream_t mz_host_stream();
+#define MZ_HOST_STREAM mzh::mz_host_stream()
+
+// ---- defined in mzhip_launch.inc
+struct DeviceCtx; // per-device state of the launchers: opaque on the host side
+constexpr int kMaxDevices = 16;
+int32_t ctx_for_current(DeviceCtx **out);
+int ctx_device(const DeviceCtx *c); // the device index `c` belongs to
+int32_t scratch_acquire(DeviceCtx *c, size_t bytes, hipStream_t s, int *slot, void **p);
+int32_t scratch_release(DeviceCtx *c, int slot, hipStream_t s);
+// mzhip_deflate_batch_level with `d_warm`: bytes in front of each piece that are hashed as history, not coded (or null)
+int32_t deflate_batch_launch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_warm, void *d_out,
+                             const uint64_t *d_out_off, const uint32_t *d_out_cap, const uint8_t *d_final, uint32_t n, int32_t level,
+                             int32_t window_log2, uint32_t *d_out_len, uint32_t *d_crc, int32_t *d_status, void *stream);
+// CRC-32 folded on the host with the product's slicing-by-4 tables (the tables are a core header's)
+uint32_t crc32_fold_host(uint32_t value, const uint8_t *p, size_t n);
+// checksums only: crc(A||B) from crc(A), crc(B), |B|
+uint32_t crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
+/* How the WRITE paths (mz_stream_zlib WRITE's segments, mzhip_prime_write's entries) cut ONE stream for the device: pieces of
+ * 16 KiB, a wave each, every piece but the stream's first with the 32 KiB in front of it as history (hashed, not coded:
+ * mz_deflate_piece's `warm`).  Up to round 6 the pieces were 64 KiB and blind to each other: a 64 KiB entry was ONE wave's 1 024
+ * dependent steps (1.8 ms at level 1; the reference's deflate: 0.5), and matches ended at every cut.  Four times the waves,
+ * and the ratio is better than before (text, level 1: 0.3349 against 0.3387; 0.3548 without the history). */
+static inline uint32_t def_stream_piece(uint64_t stream_len, int32_t level) {
+    /* (the fast class on a short stream -- one 64 KiB entry through the unmodified writer -- is all latency: 8 waves instead of 4;
+     * 0.7 % more bytes than 16 KiB pieces on text, still fewer than the 64 KiB pieces of round 5) */
+    return (level >= 0 && level <= 3 && stream_len <= (256u << 10)) ? (8u << 10) : (16u << 10);
+}
+static inline uint32_t def_stream_warm(uint64_t piece_off) { return (uint32_t)(piece_off < 32768u ? piece_off : 32768u) & ~63u; }
+
+// ---- copies on a stream, and the staging of the synchronous host-buffer calls (both sides use them)
+static inline hipError_t mz_h2d_on(hipStream_t s, void *dst, const void *src, size_t n) {
+    return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s);
+}
+static inline hipError_t mz_d2h_on(hipStream_t s, void *dst, const void *src, size_t n) {
+    const hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, s);
+    return e != hipSuccess ? e : hipStreamSynchronize(s);
+}
+static inline hipError_t mz_h2d(void *dst, const void *src, size_t n) {
+    return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, MZ_HOST_STREAM); // (pageable source: staged before the call returns)
+}
+static inline hipError_t mz_d2h(void *dst, const void *src, size_t n) {
+    const hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, MZ_HOST_STREAM);
+    return e != hipSuccess ? e : hipStreamSynchronize(MZ_HOST_STREAM);
+}
+// Staging of the synchronous host-buffer calls: a buffer of the scratch cache instead of a hipMalloc / hipFree pair
+// per call (hipFree alone is a device-wide synchronisation); released when the call returns, after its own sync.
+struct Staging {
+    DeviceCtx *c = nullptr;
+    int slot = -1;
+    void *p = nullptr;
+    int32_t get(DeviceCtx *ctx, size_t bytes) {
+        c = ctx;
+        return scratch_acquire(ctx, bytes, MZ_HOST_STREAM, &slot, &p);
+    }
+    ~Staging() {
+        if (slot >= 0) (void)scratch_release(c, slot, MZ_HOST_STREAM);
+    }
+};
+
+// ---- defined in mzhip_host.cpp: checksums of the new bytes of a decoded window (the many-wave decoders of the device TU ask them too)
+int32_t window_piece_crcs(uint8_t *base, size_t out_off, uint32_t hist, uint32_t out_len, uint32_t seg_first, uint32_t seg_stride,
+                          uint32_t *seg_crc, uint32_t seg_cap, uint32_t *nseg, uint8_t *sm, size_t seg_max);
+int32_t window_checksums(uint8_t *base, size_t out_off, uint32_t hist, uint32_t out_len, uint32_t *crc, uint32_t *adler, uint8_t *sm,
+                         size_t room, hipStream_t st = nullptr);
+
+} // namespace mzh
+
+// adler(A||B) from those of A and B and |B| (mzhip_launch.inc; shared with the C shims, shim_common.h)
+extern "C" uint32_t mzhip_adler32_combine(uint32_t ad_a, uint32_t ad_b, uint64_t len_b);
+
+#endif

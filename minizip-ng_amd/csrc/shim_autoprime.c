@@ -12,7 +12,7 @@
  *     -- every DEFLATE / LZMA / XZ entry decoded in one launch per codec, STORE entries' CRCs too;
  *   larger ones are ROLLED OVER: the tail of the file (end records + central directory) is indexed once
  *     (mzhip_zip_index_tail), the entries a codec stream would be opened for are cut -- in the order their local headers
- *     lie in the file -- into windows of about 256 MiB of compressed + decoded bytes, and a window is imaged through the
+ *     lie in the file -- into windows of about 128 MiB of compressed + decoded bytes, and a window is imaged through the
  *     reader's stream and decoded AHEAD of the reader: the window the entry at hand lies in (its first use), and the one
  *     behind it right after (the look-ahead), each as a cache generation of its own on a worker thread's pipeline
  *     (mzhip_prime_window_begin: H2D, launches, D2H of chunk i+1 / i / i-1 at once; the reader is served chunk by chunk).

@@ -3,7 +3,7 @@
 #define MZHIP_SHIM_COMMON_H
 #include <stdint.h>
 
-/* prime cache lookup (mzhip_kernels.hip): 1 = hit, for any primed method (8 DEFLATE, 14 LZMA, 95 XZ).  `head` = the
+/* prime cache lookup (mzhip_prime.inc): 1 = hit, for any primed method (8 DEFLATE, 14 LZMA, 95 XZ).  `head` = the
  * payload bytes pulled so far, `max_total_in` = the stream's TOTAL_IN_MAX (<= 0: unknown).  On a hit *pin keeps the
  * cached generation alive; hand it back with mzhip_prime_unpin() when the stream stops reading from `data`. */
 int32_t mzhip_prime_lookup3(int32_t method, int64_t payload_off, const uint8_t *head, int32_t head_len, int64_t max_total_in,

@@ -775,7 +775,7 @@ static int32_t stream_finish(mzhip_zlib *z, int64_t used) {
 /* ---- window mode, one window ahead (see the struct) ---- */
 #define MZH_LA_HIST 98304 /* bytes of out[] that go in front of the next window: the 32 KiB of history and what may not have been served yet */
 int32_t mzhip_prime_current_device(void);   /* (mzhip_prime.inc) the calling thread's device */
-void mzhip_thread_use_device(int32_t dev);  /* (mzhip_runtime.inc) ... and making it another thread's */
+void mzhip_thread_use_device(int32_t dev);  /* (mzhip_crc_host.cpp) ... and making it another thread's */
 static int8_t mzh_la_mode = -1;
 static uint64_t mzh_la_windows; /* windows taken over from a look-ahead thread, all streams (tests, reports) */
 MZHIP_API void mzhip_set_stream_lookahead(int32_t on) { __atomic_store_n(&mzh_la_mode, (int8_t)(on ? 1 : 0), __ATOMIC_RELAXED); }

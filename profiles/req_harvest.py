@@ -47,14 +47,20 @@ def load(d, tag, kernel):
 
 
 def kernel_src_hash():
-    """what names the kernels a measurement was taken on: a hash of every device source (minizip-ng_amd/csrc/*.h, *.inc, *.hip).  bench.py
+    """what names the kernels a measurement was taken on: a hash of what the kernels' translation unit is built from, in
+    minizip-ng_amd/csrc: *.hip, *_core.h, wave.h, every *.inc but mzhip_prime.inc (the kernel bodies and the launch side,
+    mzhip_launch.inc) and mzhip_runtime.h (its piece sizes shape the DEFLATE launches).  The host runtime (*.cpp, mzhip_prime.inc)
+    and the C shims (shim_*.c, shim_common.h, zip_index.c) are outside: an edit there changes no kernel and no launch.  bench.py
     computes the same and says in `traffic_source` whether the counters belong to the build it is timing."""
     import glob
     import hashlib
     h = hashlib.sha1()
     d = os.path.join(ROOT, "minizip-ng_amd", "csrc")
-    for f in sorted(glob.glob(os.path.join(d, "*.h")) + glob.glob(os.path.join(d, "*.inc")) + glob.glob(os.path.join(d, "*.hip"))):
-        if os.path.basename(f) in ("mzhip_prime.inc", "shim_common.h"):  # the host-side prime cache and the shims' glue: nothing a kernel or its launch sees
+    names = [os.path.join(d, n) for n in ("wave.h", "mzhip_runtime.h")]
+    for pat in ("*.hip", "*_core.h", "*.inc"):
+        names += glob.glob(os.path.join(d, pat))
+    for f in sorted(names):
+        if os.path.basename(f) == "mzhip_prime.inc":
             continue
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())

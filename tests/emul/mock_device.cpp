@@ -4,8 +4,9 @@
 // reference's unmodified zip layer in a container WITHOUT a GPU.  tests/emul/Makefile links it into
 // tests/emul/_build/libmockdrop.so, which only tests/test_shims_emul.py loads.  It is never part of libmzhip.so: the
 // product has no CPU path, and a GPU box runs the same tests against the real device (tests/test_gpu_dropin.py,
-// test_gpu_wrappers.py).  What it cannot cover: the prime caches and the .xz writer, whose host code lives in
-// mzhip_kernels.hip.
+// test_gpu_wrappers.py).  The READ-side prime cache is the product's own (mzhip_prime.inc, included further down over a
+// stand-in for the HIP runtime).  What it cannot cover: the write-side prime (mzhip_prime.cpp) and the .xz writer, whose
+// host code launches kernels itself (mzhip_launch.inc).
 #include <atomic>
 
 #include "emul.cpp"
@@ -343,7 +344,7 @@ MOCK_API int32_t mzhip_lzma_encode_host(const uint8_t *in, uint32_t in_len, uint
     return emul_lzma_encode(in ? in : &dummy, in_len, 0u, out, out_cap, out_len, crc);
 }
 MOCK_API int32_t mzhip_xz_encode_host(const uint8_t *, uint32_t, uint8_t *, uint32_t, uint32_t *, uint32_t *) {
-    return MZHIP_STATUS_UNSUPPORTED; /* the .xz container is laid out by host code inside mzhip_kernels.hip */
+    return MZHIP_STATUS_UNSUPPORTED; /* the .xz container is laid out by host code that launches kernels (mzhip_launch.inc) */
 }
 MOCK_API int32_t mzhip_lzma_encode_host_preset(const uint8_t *in, uint32_t in_len, int32_t preset, uint8_t *out, uint32_t out_cap,
                                                uint32_t *out_len, uint32_t *crc) {

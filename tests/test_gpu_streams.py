@@ -1,6 +1,6 @@
 """Concurrent use of the batch ABI: several host threads, each on its own HIP stream, running the two encoders that
 need per-launch device scratch (K4 tokens, K6 tokens) back to back without synchronising in between.  The scratch
-cache (scratch_acquire in mzhip_kernels.hip) must never hand two in-flight launches on different streams the same
+cache (scratch_acquire in mzhip_launch.inc) must never hand two in-flight launches on different streams the same
 buffer; every result is checked by inflating / LZMA-decoding it on the CPU."""
 import ctypes as C
 import lzma
