@@ -467,3 +467,173 @@ extern "C" int32_t emul_deflate_lazy(const uint8_t *in, uint32_t in_len, uint8_t
     return emul_deflate_ways(in, in_len, out, out_cap, final, MZ_DEF_WAYS_BEST, 0u, out_len, crc);
 }
 extern "C" uint32_t emul_deflate_lds_bytes(void) { return (uint32_t)sizeof(mz_deflate_lds); }
+
+/* ---- sequences through ONE wave's state ----
+ * The batch kernels are grids of persistent waves: a wave takes an entry index from a counter, codes that entry and takes the
+ * next, with the same LDS slice and the same scratch in HBM (mzhip_kernels.hip, the for (;;) loops).  The entry points above
+ * hand every call fresh, poisoned state; these allocate and poison the wave's state ONCE and run k entries through it in
+ * order, so that what an entry leaves behind is what the next one finds. */
+extern "C" void emul_inflate_seq(uint32_t k, const uint8_t *const *in, const uint32_t *in_len, uint8_t *const *out,
+                                 const uint32_t *out_cap, const uint32_t *st_in /* 4 words per entry: the resumable kernel; or null */,
+                                 uint32_t *st_out /* 4 words per entry, or null */, uint32_t *out_len, uint32_t *in_used,
+                                 uint32_t *crc, int32_t *status) {
+    ready();
+    mz_inflate_lds *L = (mz_inflate_lds *)malloc(sizeof(mz_inflate_lds));
+    memset(L, 0xA5, sizeof(*L));
+    uint8_t *rec = (uint8_t *)malloc(MZ_REC_BYTES + 1024);
+    memset(rec, 0x5A, MZ_REC_BYTES + 1024);
+    for (uint32_t e = 0; e < k; e++) {
+        mz_inflate_state a, b;
+        memset(&a, 0, sizeof(a));
+        memset(&b, 0, sizeof(b));
+        if (st_in) memcpy(&a, st_in + 4 * e, sizeof(a));
+        mz_inflate_result r;
+        mz_inflate_entry(in[e], in_len[e], out[e], out_cap[e], L, g_tabs.byte_tab, &g_tabs, 1u, rec, st_in ? &a : (const mz_inflate_state *)0,
+                         st_out ? &b : (mz_inflate_state *)0, &r, (const mz_inflate_par *)0);
+        if (st_out) memcpy(st_out + 4 * e, &b, sizeof(b));
+        out_len[e] = r.out_len;
+        in_used[e] = r.in_used;
+        crc[e] = r.crc;
+        status[e] = r.status;
+    }
+    free(rec);
+    free(L);
+}
+
+/* mzhip_lzma_batch: a wave of the slot kernel takes every entry; what it gives back (MZHIP_RETRY) goes, in the order given
+ * back, through a wave of the full-model kernel.  One LDS slice and one scratch (sprobs / xprobs) per kernel for the whole
+ * sequence.  retried[e]: whether entry e went through the second wave. */
+extern "C" void emul_lzma_seq(uint32_t k, const uint8_t *const *in, const uint32_t *in_len, uint8_t *const *out, const uint32_t *out_cap,
+                              const int64_t *max_out, uint32_t *out_len, uint32_t *in_used, uint32_t *crc, int32_t *status,
+                              uint32_t *retried) {
+    ready();
+    mz_lzma_lds_s *S = (mz_lzma_lds_s *)malloc(sizeof(mz_lzma_lds_s));
+    memset(S, 0xA5, sizeof(*S));
+    uint16_t *sprobs = (uint16_t *)malloc(MZ_LZMA_SPROBS * sizeof(uint16_t));
+    memset(sprobs, 0x5A, MZ_LZMA_SPROBS * sizeof(uint16_t));
+    mz_lzma_lds *L = (mz_lzma_lds *)malloc(sizeof(mz_lzma_lds));
+    memset(L, 0xA5, sizeof(*L));
+    uint16_t *xprobs = (uint16_t *)malloc(MZ_LZMA_XPROBS * sizeof(uint16_t));
+    memset(xprobs, 0x5A, MZ_LZMA_XPROBS * sizeof(uint16_t));
+    for (uint32_t e = 0; e < k; e++) {
+        mz_lzma_result r;
+        mz_lzma_entry_s(in[e], in_len[e], out[e], out_cap[e], max_out[e], S, g_tabs.byte_tab, &g_tabs, sprobs, &r);
+        out_len[e] = r.out_len;
+        in_used[e] = r.in_used;
+        crc[e] = r.crc;
+        status[e] = r.status;
+        retried[e] = r.status == MZHIP_RETRY;
+    }
+    for (uint32_t e = 0; e < k; e++) {
+        if (!retried[e]) continue;
+        mz_lzma_result r;
+        mz_lzma_entry(in[e], in_len[e], out[e], out_cap[e], max_out[e], L, g_tabs.byte_tab, &g_tabs, xprobs, &r);
+        out_len[e] = r.out_len;
+        in_used[e] = r.in_used;
+        crc[e] = r.crc;
+        status[e] = r.status;
+    }
+    free(xprobs);
+    free(L);
+    free(sprobs);
+    free(S);
+}
+
+extern "C" void emul_xz_seq(uint32_t k, const uint8_t *const *in, const uint32_t *in_len, uint8_t *const *out, const uint32_t *out_cap,
+                            const int64_t *max_out, uint32_t *out_len, uint32_t *in_used, uint32_t *crc, int32_t *status) {
+    ready();
+    mz_xz_lds *L = (mz_xz_lds *)malloc(sizeof(mz_xz_lds));
+    memset(L, 0xA5, sizeof(*L));
+    mzhip_crc64_table_init(L->crc64_tab); /* (k_xz_batch fills it once, in front of its loop) */
+    uint16_t *prx = (uint16_t *)malloc(MZ_LZMA_XPROBS * sizeof(uint16_t));
+    memset(prx, 0x5A, MZ_LZMA_XPROBS * sizeof(uint16_t));
+    for (uint32_t e = 0; e < k; e++) {
+        mz_lzma_result r;
+        mz_xz_entry(in[e], in_len[e], out[e], out_cap[e], max_out[e], L, g_tabs.byte_tab, &g_tabs, prx, &r);
+        out_len[e] = r.out_len;
+        in_used[e] = r.in_used;
+        crc[e] = r.crc;
+        status[e] = r.status;
+    }
+    free(prx);
+    free(L);
+}
+
+/* K4, one class per sequence (ways / parse as emul_deflate, emul_deflate_lazy, emul_deflate_best): one LDS slice, one token
+ * block and one xhead */
+extern "C" void emul_deflate_seq(uint32_t k, const uint8_t *const *in, const uint32_t *in_len, uint8_t *const *out,
+                                 const uint32_t *out_cap, const uint32_t *final, uint32_t ways, uint32_t parse, uint32_t *out_len,
+                                 uint32_t *crc, int32_t *status) {
+    ready();
+    mz_deflate_lds *L = (mz_deflate_lds *)malloc(sizeof(mz_deflate_lds));
+    memset(L, 0xA5, sizeof(*L));
+    uint16_t *xh = (uint16_t *)malloc((MZ_DEF_WAYS_BEST - 1u) * sizeof(uint16_t) << MZ_DEF_HBITS);
+    memset(xh, 0x5A, (MZ_DEF_WAYS_BEST - 1u) * sizeof(uint16_t) << MZ_DEF_HBITS);
+    uint32_t *tok = (uint32_t *)malloc(MZ_DEF_BLOCK * sizeof(uint32_t));
+    memset(tok, 0x5A, MZ_DEF_BLOCK * sizeof(uint32_t));
+    for (uint32_t e = 0; e < k; e++) {
+        mz_deflate_result r;
+        if (parse) mz_deflate_piece<1u>(in[e], in_len[e], 0u, out[e], out_cap[e], final[e], tok, L, g_tabs.byte_tab, &g_tabs, ways, ways > 1u ? xh : (uint16_t *)0, g_def_max_dist, &r);
+        else mz_deflate_piece<0u>(in[e], in_len[e], 0u, out[e], out_cap[e], final[e], tok, L, g_tabs.byte_tab, &g_tabs, ways, ways > 1u ? xh : (uint16_t *)0, g_def_max_dist, &r);
+        out_len[e] = r.out_len;
+        crc[e] = r.crc;
+        status[e] = r.status;
+    }
+    free(tok);
+    free(xh);
+    free(L);
+}
+
+/* K6's three passes, each with ONE wave: the chain pass over every entry (one chain_head table), the tokenizer over every
+ * block of every entry (one head slice, one xhead), the range coder over every entry (one model slice).  Links and tokens
+ * are per entry on the device too. */
+extern "C" void emul_lzma_enc_seq(uint32_t k, const uint8_t *const *in, const uint32_t *in_len, const uint32_t *mode, uint32_t ways,
+                                  uint8_t *const *out, const uint32_t *out_cap, uint32_t *out_len, uint32_t *crc, int32_t *status) {
+    ready();
+    uint32_t **tok = (uint32_t **)calloc(k ? k : 1, sizeof(uint32_t *));
+    uint32_t **ntok = (uint32_t **)calloc(k ? k : 1, sizeof(uint32_t *));
+    uint32_t **links = (uint32_t **)calloc(k ? k : 1, sizeof(uint32_t *));
+    uint32_t *head = (uint32_t *)malloc(sizeof(uint32_t) << MZ_LZE_FAR_HBITS);
+    memset(head, 0xA5, sizeof(uint32_t) << MZ_LZE_FAR_HBITS);
+    for (uint32_t e = 0; e < k; e++) {
+        const uint32_t nblocks = (in_len[e] + MZ_DEF_BLOCK - 1) / MZ_DEF_BLOCK;
+        tok[e] = (uint32_t *)malloc((size_t)(nblocks ? nblocks : 1) * MZ_DEF_BLOCK * sizeof(uint32_t));
+        ntok[e] = (uint32_t *)calloc(nblocks ? nblocks : 1, sizeof(uint32_t));
+        if (mode[e] == 0u && in_len[e] > MZ_DEF_BLOCK) {
+            links[e] = (uint32_t *)malloc((size_t)nblocks * MZ_DEF_BLOCK * sizeof(uint32_t));
+            memset(links[e], 0xA5, (size_t)nblocks * MZ_DEF_BLOCK * sizeof(uint32_t));
+            mz_lz_chain(in[e], in_len[e], links[e], head);
+        }
+    }
+    free(head);
+    mz_lz_tok_lds *T = (mz_lz_tok_lds *)malloc(sizeof(mz_lz_tok_lds));
+    memset(T, 0xA5, sizeof(*T));
+    const size_t xbytes = (MZ_DEF_WAYS_BEST - 1u) * (sizeof(uint16_t) << MZ_DEF_HBITS);
+    uint16_t *xhead = (uint16_t *)malloc(xbytes);
+    memset(xhead, 0xA5, xbytes);
+    for (uint32_t e = 0; e < k; e++) {
+        const uint32_t nblocks = (in_len[e] + MZ_DEF_BLOCK - 1) / MZ_DEF_BLOCK;
+        for (uint32_t b = 0; b < nblocks; b++) {
+            const uint32_t lo = b * MZ_DEF_BLOCK, hi = (in_len[e] - lo < MZ_DEF_BLOCK) ? in_len[e] : lo + MZ_DEF_BLOCK;
+            ntok[e][b] = mz_lz_tokenize(in[e], lo, hi, tok[e] + (size_t)b * MZ_DEF_BLOCK, T, ways, ways > 1u ? xhead : (uint16_t *)0, links[e], far_depth_for(ways));
+        }
+    }
+    free(xhead);
+    free(T);
+    mz_lzma_lds *L = (mz_lzma_lds *)malloc(sizeof(mz_lzma_lds));
+    memset(L, 0xA5, sizeof(*L));
+    for (uint32_t e = 0; e < k; e++) {
+        mz_lzma_enc_result r;
+        mz_lzma_rc_encode(in[e], in_len[e], tok[e], ntok[e], mode[e], out[e], out_cap[e], L, g_tabs.byte_tab, &g_tabs, &r);
+        out_len[e] = r.out_len;
+        crc[e] = r.crc;
+        status[e] = r.status;
+        free(tok[e]);
+        free(ntok[e]);
+        free(links[e]);
+    }
+    free(L);
+    free(tok);
+    free(ntok);
+    free(links);
+}

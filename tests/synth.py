@@ -329,18 +329,213 @@ def xz_filter_cases():
     return cases
 
 
-def long_code_payloads():
+def long_code_payloads(size=200000):
     """(name, data, raw_deflate): streams whose dynamic Huffman codes reach 13-15 bits and use many symbols, so the
     decoder's second-level literal/length tables are exercised up to their capacity (zlib Z_HUFFMAN_ONLY / level 9 on
-    data with geometric byte statistics, all 256 byte values present)."""
+    data with geometric byte statistics, all 256 byte values present).  size: bytes drawn (the rare symbols are the 512
+    bytes behind them, so the code lengths stay as long at a tenth of the default)."""
     out = []
     for seed, ratio in ((1, 0.5), (2, 0.6), (3, 0.7), (4, 0.8)):
         rnd = np.random.RandomState(seed)
         p = ratio ** np.arange(256, dtype=np.float64)
         p /= p.sum()
         perm = rnd.permutation(256)
-        d = perm[rnd.choice(256, size=200000, p=p)].astype(np.uint8).tobytes()
+        d = perm[rnd.choice(256, size=size, p=p)].astype(np.uint8).tobytes()
         d += bytes(range(256)) * 2                      # every byte value at least twice
         for strat, nm in ((zlib.Z_HUFFMAN_ONLY, "huff"), (zlib.Z_DEFAULT_STRATEGY, "l9")):
             out.append(("geom%.1f/%s" % (ratio, nm), d, deflate_raw(d, level=9, strategy=strat)))
     return out
+
+
+# ---- streams made by hand: fixed-Huffman blocks of chosen tokens (zlib never emits distance 32768) ----------------------
+
+_LBASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
+_LEXT = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0]
+_DBASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193,
+          12289, 16385, 24577]
+_DEXT = [0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13]
+
+
+def fixed_stream(tokens):
+    """tokens: int (a literal) or (length, distance) -> one final fixed-Huffman block (RFC 1951 3.2.6)"""
+    acc, nb, out = 0, 0, bytearray()
+
+    def put(v, n):                       # n bits of v, least significant first
+        nonlocal acc, nb
+        acc |= v << nb
+        nb += n
+        while nb >= 8:
+            out.append(acc & 255)
+            acc >>= 8
+            nb -= 8
+
+    def code(v, n):                      # a Huffman code: most significant bit first
+        put(int(format(v, "0%db" % n)[::-1], 2), n)
+
+    def sym(s):
+        if s < 144: code(0x30 + s, 8)
+        elif s < 256: code(0x190 + s - 144, 9)
+        elif s < 280: code(s - 256, 7)
+        else: code(0xC0 + s - 280, 8)
+
+    put(1, 1)
+    put(1, 2)
+    for t in tokens:
+        if isinstance(t, int):
+            sym(t)
+            continue
+        ln, dist = t
+        k = max(i for i in range(29) if _LBASE[i] <= ln) if ln < 258 else 28
+        sym(257 + k)
+        put(ln - _LBASE[k], _LEXT[k])
+        k = max(i for i in range(30) if _DBASE[i] <= dist)
+        code(k, 5)
+        put(dist - _DBASE[k], _DEXT[k])
+    sym(256)
+    if nb:
+        out.append(acc & 255)
+    return bytes(out)
+
+
+def hand_made():
+    rnd = np.random.RandomState(21)
+    lit = [int(v) for v in rnd.randint(0, 256, size=32768)]
+    c = corpus()
+    cases = []
+    cases.append(("ends_in_258_match", fixed_stream(list(c[:700]) + [(258, 300)])))
+    cases.append(("ends_in_258_run", fixed_stream([65, (258, 1)])))
+    cases.append(("runs_258", fixed_stream([66] + [(258, 1)] * 40)))
+    cases.append(("dist_32768", fixed_stream(lit + [(258, 32768), (3, 32768), 7, (100, 32768)])))
+    cases.append(("dist_32768_then_258_end", fixed_stream(lit + [5] * 9 + [(258, 32768)])))
+    return cases
+
+
+# ---- wave reuse: a table of small, unique streams with their reference results ---------------------------------------
+_REUSE = {}
+
+
+def _kind(name, z, cap, st, used, out, max_out=-1, refused=None):
+    """one decoder kind: the stream, the room it is given, and what the reference makes of it"""
+    return dict(name=name, z=z, cap=cap, max_out=max_out, status=st, in_used=used, out_len=len(out), data=out, crc=zlib.crc32(out),
+                refused=refused, long=cap > 32768)
+
+
+def reuse_kinds():
+    """{"deflate" | "lzma" | "xz": [kind, ...], "enc": [(name, bytes), ...]}: what tests/test_kernel_emul.py runs in pairs through
+    one wave's state and tests/test_gpu_wave_reuse.py draws its launches from.  A decoder kind is a dict: name, z (the stream),
+    cap (out_cap), max_out, refused (None for a good kind, else the status the kind is named after), long (more than 32 KiB
+    of room: the kinds a launch of thousands of entries takes one entry in 97 from) and the reference result: status, in_used, out_len, crc from the oracle restatement, data = the bytes (zlib /
+    lzma say the same of every good kind: test_kernel_emul.test_reuse_kinds_are_what_they_claim).  Built once per process;
+    nobody changes it."""
+    if _REUSE:
+        return _REUSE
+    import lzma
+
+    import oracle
+    from tests.test_oracle import INCOMPLETE_DISTANCE_SET, _zip_lzma
+
+    c = corpus()
+    rnd = np.random.RandomState(97)
+    noise = rnd.bytes(3000)
+
+    # DEFLATE
+    def dk(name, z, cap, refused=None):
+        st, used, out = oracle.inflate_raw(z, cap)
+        return _kind(name, z, cap, st, used, out, refused=refused)
+
+    def good(name, data, z):
+        return dk(name, z, len(data))
+
+    dyn = deflate_raw(c[20000:23000])
+    hm = dict(hand_made())
+    dist_data = zlib.decompress(hm["dist_32768"], -15)
+    co = zlib.compressobj(6, zlib.DEFLATED, -15, 8)
+    flushed = b"".join(co.compress(c[40000 + 90 * i:40000 + 90 * (i + 1)]) + co.flush(zlib.Z_FULL_FLUSH if i % 3 == 2 else zlib.Z_SYNC_FLUSH)
+                       for i in range(30)) + co.flush()
+    D = [good("empty", b"", deflate_raw(b"")), good("one_byte", b"x", deflate_raw(b"x")),
+         good("stored", c[:3000], stored_blocks(c[:3000], block=1000)),
+         good("fixed", c[30000:32000], deflate_raw(c[30000:32000], strategy=zlib.Z_FIXED)),
+         good("dynamic_short", c[20000:23000], dyn)]
+    D += [good("long_codes/" + n, d, z) for n, d, z in long_code_payloads(20000)]
+    D += [good("flushed_blocks", c[40000:40000 + 2700], flushed), good("dist_32768", dist_data, hm["dist_32768"]),
+          good("runs_258", b"B" * (1 + 258 * 40), hm["runs_258"]),
+          good("text_64k_l9", c[9000:9000 + 65536], deflate_raw(c[9000:9000 + 65536], level=9)),
+          good("noise", noise, deflate_raw(noise))]
+    dh = deflate_raw(bytes(range(256)) * 4 + c[:1500])          # every literal in use: a long dynamic header
+    stored = stored_blocks(c[:3000], block=1000)
+    D += [dk("cut_mid_block", dyn[:len(dyn) // 2], 4000, -5), dk("cut_in_dynamic_header", dh[:20], 4000, -5),
+          dk("cut_stored", stored[:1500], 4000, -5),
+          dk("invalid_code", fixed_stream(list(c[:300]) + [286] + list(c[300:400])), 4000, -3),        # (symbol 286 has a code and no meaning)
+          dk("stored_bad_nlen", stored[:1005] + bytes([stored[1005], stored[1006], stored[1007] ^ 1]) + stored[1008:], 4000, -3),
+          dk("far0", fixed_stream([(258, 1), 65, 66]), 4000, -3),
+          dk("far100", fixed_stream(list(c[:100]) + [(258, 32768), 67]), 4000, -3),
+          dk("incomplete_distance_set_0", INCOMPLETE_DISTANCE_SET[0], 4000, -3),
+          dk("incomplete_distance_set_1", INCOMPLETE_DISTANCE_SET[1], 26000, -3),       # (25 286 bytes of matches come first)
+          dk("out_cap_one_short", dyn, 3000 - 1, -200)]
+
+    # LZMA (ZIP method 14)
+    def lk(name, z, cap, max_out=-1, refused=None):
+        st, used, out = oracle.lzma_zip_decode(z, cap, max_out)
+        if refused == -5 and st == -3:
+            # The restatement answers what mz_stream_lzma_read answers, and that folds liblzma's LZMA_BUF_ERROR (the input ends
+            # inside a valid stream) into MZ_DATA_ERROR (mz_strm_lzma.c:236).  The device says which of the two it was
+            # (lzma_entry.inc `finish`: -5), as liblzma does; test_reuse_kinds_are_what_they_claim holds this kind against
+            # liblzma: no error, and no end of stream either.
+            st = -5
+        return _kind(name, z, cap, st, used, out, max_out=max_out, refused=refused)
+
+    def alone(d, **f):
+        raw = lzma.compress(d, format=lzma.FORMAT_ALONE, filters=[dict(id=lzma.FILTER_LZMA1, preset=6, **f)])
+        return bytes([5, 2, 5, 0]) + raw[:5] + raw[13:]
+
+    d = c[50000:53000] + bytes(range(256)) * 3
+    Z = [lk("lc%dlp%dpb%d" % p, alone(d, lc=p[0], lp=p[1], pb=p[2]), len(d), len(d))
+         for p in ((4, 0, 2), (3, 1, 2), (0, 4, 0), (2, 2, 4), (1, 3, 1), (0, 0, 0), (3, 0, 4), (3, 0, 2))]
+    text = _zip_lzma(c[60000:64000])
+    Z += [lk("run", _zip_lzma(b"A" * 4000), 4000, 4000), lk("text", text, 4000), lk("noise", _zip_lzma(noise), 3000, 3000),
+          lk("max_out_clamp", text, 4000, 2500)]
+    bad = None
+    for seed in range(200):              # a stream whose first packet is a match (rep0 beyond the empty dictionary)
+        cand = text[:9] + b"\x00" + np.random.RandomState(seed).bytes(40)
+        r = oracle.lzma_zip_decode(cand, 4000, -1)
+        if r[0] == -3 and r[2] == b"":
+            bad = cand
+            break
+    assert bad is not None
+    props = bytearray(text)
+    props[4] = 4 + 9 * 1 + 45 * 2        # lc 4, lp 1
+    Z += [lk("first_packet_match", bad, 4000, refused=-3), lk("cut", text[:len(text) // 2], 4000, refused=-5),
+          lk("lc_plus_lp_5", bytes(props), 4000, refused=-3), lk("first_coder_byte", text[:9] + b"\x01" + text[10:], 4000, refused=-3),
+          lk("out_cap_one_short", text, 3999, refused=-200)]
+
+    # .xz (method 95)
+    def xk(name, x, cap, max_out=-1, refused=None):
+        st, used, out = oracle.xz_decode(x, cap, max_out)
+        return _kind(name, x, cap, st, used, out, max_out=max_out, refused=refused)
+
+    every = {n: (dd, x) for n, dd, x in xz_cases()}            # (xz_filter_cases() is part of it)
+    X = []
+    for n in ("one/check0", "one/check1", "one/check4", "one/check10", "empty/check1", "one/lc0lp4pb2", "filter/x86/5000", "filter/arm/17",
+              "filter/ia64/5000", "filter/delta1+delta2+arm", "multi-block"):
+        dd, x = every[n]
+        X.append(xk(n, x, len(dd)))
+    t4 = c[70000:74000]
+    for chk in (lzma.CHECK_NONE, lzma.CHECK_CRC32, lzma.CHECK_CRC64, lzma.CHECK_SHA256):
+        X.append(xk("text4k/check%d" % chk, lzma.compress(t4, format=lzma.FORMAT_XZ, check=chk, preset=6), len(t4)))
+    parts = [c[1000:2500], noise[:700], b"", c[3000:4000]]
+    X.append(xk("multi-block-small-sha", xz_join([lzma.compress(p, format=lzma.FORMAT_XZ, check=lzma.CHECK_SHA256) for p in parts]), 3200))
+    X.append(xk("text4k/lc1lp3", lzma.compress(t4, format=lzma.FORMAT_XZ, filters=[{"id": lzma.FILTER_LZMA2, "lc": 1, "lp": 3, "pb": 1, "dict_size": 4096}]), len(t4)))
+    X.append(xk("max_out_clamp", X[12]["z"], len(t4), 2500))
+    good_x = lzma.compress(t4, format=lzma.FORMAT_XZ, check=lzma.CHECK_CRC64, preset=6)
+    flip = bytearray(good_x)
+    flip[-12 - 8 - 8 + 3] ^= 0x40          # inside the block's CRC-64 (index 8 bytes, footer 12)
+    X += [xk("bad_chain/" + n, x, 4000, refused=-3) for n, x in xz_bad_chain_cases()]
+    X += [xk("cut", good_x[:len(good_x) // 2], 4000, refused=-5), xk("check_flipped", bytes(flip), 4000, refused=-3),
+          xk("out_cap_one_short", good_x, len(t4) - 1, refused=-200)]
+
+    # encoder inputs
+    E = [("empty", b""), ("one_byte", b"q"), ("run_258", b"z" * 258), ("text", c[80000:83000]), ("noise", noise[:2000]),
+         ("text+noise", c[90000:91500] + noise[:1000] + c[91500:92000]), ("text_64k", c[100000:100000 + 65536]),
+         ("text_70000", c[200000:270000])]
+    _REUSE.update(deflate=D, lzma=Z, xz=X, enc=E)
+    return _REUSE

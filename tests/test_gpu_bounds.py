@@ -18,6 +18,7 @@ import pytest
 
 import oracle
 from tests import synth
+from tests.synth import fixed_stream, hand_made  # (made by hand: tests/synth.py; tests/asan_bounds.py takes them from here)
 from tests.test_oracle import _zip_lzma
 
 pytestmark = pytest.mark.gpu
@@ -38,56 +39,6 @@ def gpu():
           % (", ".join("%s %d" % kv for kv in sorted(COUNTS.items())), time.time() - t0))
 
 
-# ---- streams made by hand: fixed-Huffman blocks of chosen tokens (zlib never emits distance 32768) ----------------------
-
-_LBASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
-_LEXT = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0]
-_DBASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193,
-          12289, 16385, 24577]
-_DEXT = [0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13]
-
-
-def fixed_stream(tokens):
-    """tokens: int (a literal) or (length, distance) -> one final fixed-Huffman block (RFC 1951 3.2.6)"""
-    acc, nb, out = 0, 0, bytearray()
-
-    def put(v, n):                       # n bits of v, least significant first
-        nonlocal acc, nb
-        acc |= v << nb
-        nb += n
-        while nb >= 8:
-            out.append(acc & 255)
-            acc >>= 8
-            nb -= 8
-
-    def code(v, n):                      # a Huffman code: most significant bit first
-        put(int(format(v, "0%db" % n)[::-1], 2), n)
-
-    def sym(s):
-        if s < 144: code(0x30 + s, 8)
-        elif s < 256: code(0x190 + s - 144, 9)
-        elif s < 280: code(s - 256, 7)
-        else: code(0xC0 + s - 280, 8)
-
-    put(1, 1)
-    put(1, 2)
-    for t in tokens:
-        if isinstance(t, int):
-            sym(t)
-            continue
-        ln, dist = t
-        k = max(i for i in range(29) if _LBASE[i] <= ln) if ln < 258 else 28
-        sym(257 + k)
-        put(ln - _LBASE[k], _LEXT[k])
-        k = max(i for i in range(30) if _DBASE[i] <= dist)
-        code(k, 5)
-        put(dist - _DBASE[k], _DEXT[k])
-    sym(256)
-    if nb:
-        out.append(acc & 255)
-    return bytes(out)
-
-
 def zlib_inflate(z, cap=None):
     """the host reference: (status class, bytes) of a raw-DEFLATE stream through zlib"""
     d = zlib.decompressobj(-15)
@@ -96,19 +47,6 @@ def zlib_inflate(z, cap=None):
     except zlib.error:
         return -3, b""
     return (0 if d.eof else -5), out
-
-
-def hand_made():
-    rnd = np.random.RandomState(21)
-    lit = [int(v) for v in rnd.randint(0, 256, size=32768)]
-    c = synth.corpus()
-    cases = []
-    cases.append(("ends_in_258_match", fixed_stream(list(c[:700]) + [(258, 300)])))
-    cases.append(("ends_in_258_run", fixed_stream([65, (258, 1)])))
-    cases.append(("runs_258", fixed_stream([66] + [(258, 1)] * 40)))
-    cases.append(("dist_32768", fixed_stream(lit + [(258, 32768), (3, 32768), 7, (100, 32768)])))
-    cases.append(("dist_32768_then_258_end", fixed_stream(lit + [5] * 9 + [(258, 32768)])))
-    return cases
 
 
 # ---- launch helpers ----------------------------------------------------------------------------------------------------

@@ -111,7 +111,8 @@ def test_lzma_every_lc_lp_pb(gpu):
     for lc, lp, pb in combos:
         raw = pylzma.compress(d, format=pylzma.FORMAT_ALONE, filters=[dict(id=pylzma.FILTER_LZMA1, preset=6, lc=lc, lp=lp, pb=pb)])
         pays.append(bytes([5, 2, 5, 0]) + raw[:5] + raw[13:])
-    pays = pays * 40                      # more entries than one wave: the scratch is per resident wave
+    pays = pays * 40                      # 320 entries: a wave each (the scratch is per resident wave); waves that take a second
+                                          # entry are the business of tests/test_gpu_wave_reuse.py
     b, h_out, out_len, in_used, crc, status = run_lzma(gpu, pays, [len(d) + 8] * len(pays), [len(d)] * len(pays))
     for i, z in enumerate(pays):
         assert (status[i], out_len[i], in_used[i], crc[i]) == (0, len(d), len(z), zlib.crc32(d)), (i, combos[i % len(combos)])

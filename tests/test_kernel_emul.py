@@ -1140,3 +1140,288 @@ def test_inflate_resume_small_windows(emu):
                 assert new or (so[0], so[1]) != state[:2], (window, name, len(got), "no progress")
                 state = (so[0], so[1], min(len(got), 32768), 1)
             assert bytes(got) == d, (window, name)
+
+
+# ---- sequences through ONE wave's state (tests/emul/emul.cpp emul_*_seq) ------------------------------------------------
+# A batch kernel is a grid of persistent waves: a wave takes an entry, codes it and takes the next one with the same LDS slice
+# and the same scratch.  Everything above hands every call fresh, poisoned state: that finds a read of state nobody wrote, not a
+# read of what the PREVIOUS entry wrote.  Here the state is allocated and poisoned once and entries follow each other through it.
+
+_vp = C.c_void_p
+ENC_CLASSES = (("fast", 1, 0), ("lazy", 4, 0), ("best", 4, 1))       # K4: (ways, parse) as emul_deflate / _lazy / _best
+
+
+def _seq_api(L):
+    L.emul_inflate_seq.argtypes = [C.c_uint32] + [_vp] * 10
+    L.emul_lzma_seq.argtypes = [C.c_uint32] + [_vp] * 10
+    L.emul_xz_seq.argtypes = [C.c_uint32] + [_vp] * 9
+    L.emul_deflate_seq.argtypes = [C.c_uint32] + [_vp] * 5 + [C.c_uint32, C.c_uint32] + [_vp] * 3
+    L.emul_lzma_enc_seq.argtypes = [C.c_uint32] + [_vp] * 3 + [C.c_uint32] + [_vp] * 5
+    for fn in (L.emul_inflate_seq, L.emul_lzma_seq, L.emul_xz_seq, L.emul_deflate_seq, L.emul_lzma_enc_seq):
+        fn.restype = None
+    return L
+
+
+def _seq(L, fam, ents, resume=False, ways=1, parse=0):
+    """The entries (dicts: z = input, cap = out_cap and, by family, max_out / hist + state) through ONE wave's state, in order.
+    Every entry lies in a _Guarded of its own -- the seeded pattern of gpu_util.guard_pattern around and under it -- and its
+    guards are checked.  -> per entry (status, in_used, out_len, crc, the whole out region afterwards, stop state)"""
+    k = len(ents)
+    gs = []
+    for e in ents:
+        g = _Guarded(e["z"], e["cap"], mis=len(e["z"]) % 4, omis=e["cap"] % 4)
+        h = e.get("hist", b"")
+        if h:                                                # the history of a window is the caller's
+            g.out[g.o0:g.o0 + len(h)] = np.frombuffer(h, dtype=np.uint8)
+            g.out0 = g.out.copy()
+        gs.append(g)
+    pin = np.array([g.a.ctypes.data + g.i0 for g in gs], dtype=np.uint64)
+    pout = np.array([g.out.ctypes.data + g.o0 for g in gs], dtype=np.uint64)
+    in_len = np.array([len(e["z"]) for e in ents], dtype=np.uint32)
+    cap = np.array([e["cap"] for e in ents], dtype=np.uint32)
+    out_len, in_used, crc, status = (np.full(k, 0x5EED5EED, dtype=np.uint32) for _ in range(4))
+    stop = np.zeros((k, 4), dtype=np.uint32)
+    p = lambda a: a.ctypes.data
+    if fam == "deflate":
+        st_in = np.array([e.get("state", (0, 0, 0, 0)) for e in ents], dtype=np.uint32).reshape(k, 4)
+        L.emul_inflate_seq(k, p(pin), p(in_len), p(pout), p(cap), p(st_in) if resume else None, p(stop) if resume else None,
+                           p(out_len), p(in_used), p(crc), p(status))
+    elif fam in ("lzma", "xz"):
+        mo = np.array([e["max_out"] for e in ents], dtype=np.int64)
+        if fam == "lzma":
+            retried = np.zeros(k, dtype=np.uint32)
+            L.emul_lzma_seq(k, p(pin), p(in_len), p(pout), p(cap), p(mo), p(out_len), p(in_used), p(crc), p(status), p(retried))
+        else:
+            L.emul_xz_seq(k, p(pin), p(in_len), p(pout), p(cap), p(mo), p(out_len), p(in_used), p(crc), p(status))
+    elif fam == "k4":
+        fin = np.ones(k, dtype=np.uint32)
+        in_used[:] = 0
+        L.emul_deflate_seq(k, p(pin), p(in_len), p(pout), p(cap), p(fin), ways, parse, p(out_len), p(crc), p(status))
+    else:
+        mode = np.zeros(k, dtype=np.uint32)
+        in_used[:] = 0
+        L.emul_lzma_enc_seq(k, p(pin), p(in_len), p(mode), ways, p(pout), p(cap), p(out_len), p(crc), p(status))
+    res = []
+    for i, (e, g) in enumerate(zip(ents, gs)):
+        st = int(status.view(np.int32)[i])
+        valid = int(out_len[i]) if (st == 0 or not resume) else int(stop[i][2])
+        g.check(st, valid, slack_ok=e.get("max_out", -1) >= 0)
+        res.append((st, int(in_used[i]), int(out_len[i]), int(crc[i]), g.out[g.o0:g.o0 + e["cap"]].tobytes(), tuple(int(v) for v in stop[i])))
+    return res
+
+
+def _is_reference(kd, r, what):
+    """status as the reference names it; a status-0 entry's consumed count, length, CRC and every byte (what the other words
+    hold behind a refusal is not part of include/mzhip.h: there the entry alone on fresh state is the yardstick)"""
+    assert r[0] == kd["status"], (what, kd["name"], r[0], kd["status"])
+    if kd["status"] == 0:
+        assert r[1:4] == (kd["in_used"], kd["out_len"], kd["crc"]), (what, kd["name"], r[1:4], (kd["in_used"], kd["out_len"], kd["crc"]))
+        assert r[4][:kd["out_len"]] == kd["data"], (what, kd["name"], "bytes")
+
+
+def _every_ordered_pair(L, fam, kinds, tag):
+    alone = [_seq(L, fam, [kd])[0] for kd in kinds]
+    for kd, r in zip(kinds, alone):
+        _is_reference(kd, r, (tag, "alone"))
+    for i, a in enumerate(kinds):
+        for j, b in enumerate(kinds):
+            got = _seq(L, fam, [a, b, a])
+            for pos, (r, x) in enumerate(zip(got, (i, j, i))):
+                what = (tag, "%s, %s, %s" % (a["name"], b["name"], a["name"]), "entry %d" % pos)
+                _is_reference(kinds[x], r, what)
+                assert r[:4] == alone[x][:4], (what, "differs from the entry alone on fresh state", r[:4], alone[x][:4])
+                assert r[4] == alone[x][4], (what, "output region differs from the entry alone on fresh state")
+
+
+def _huffman_max_len(freq):
+    """longest code of an optimal prefix code for the given symbol counts"""
+    import heapq
+
+    h = [(f, 0) for f in freq if f]
+    heapq.heapify(h)
+    while len(h) > 1:
+        a, b = heapq.heappop(h), heapq.heappop(h)
+        heapq.heappush(h, (a[0] + b[0], max(a[1], b[1]) + 1))
+    return h[0][1]
+
+
+def test_reuse_kinds_are_what_they_claim():
+    import lzma as pylzma
+
+    K = synth.reuse_kinds()
+    for fam in ("deflate", "lzma", "xz"):
+        names = [kd["name"] for kd in K[fam]]
+        assert len(set(names)) == len(names)
+        assert len(set((kd["z"], kd["cap"], kd["max_out"]) for kd in K[fam])) == len(names), fam
+        for kd in K[fam]:
+            assert kd["status"] == (kd["refused"] or 0), (fam, kd["name"], kd["status"], kd["refused"])
+            assert kd["crc"] == oracle.crc32(kd["data"]) and kd["out_len"] == len(kd["data"]) <= kd["cap"]
+            assert kd["refused"] is None or not kd["long"], (fam, kd["name"])
+    assert 3 * sum(kd["refused"] is not None for kd in K["deflate"]) >= len(K["deflate"])
+    assert 4 * sum(kd["refused"] is not None for kd in K["lzma"]) >= len(K["lzma"])
+    assert {kd["refused"] for kd in K["deflate"]} == {None, -3, -5, -200}
+    for kd in K["deflate"]:
+        dec = zlib.decompressobj(-15)
+        if kd["refused"] == -3:
+            with pytest.raises(zlib.error):
+                dec.decompress(kd["z"])
+            continue
+        out = dec.decompress(kd["z"])
+        if kd["refused"] is None:
+            assert dec.eof and not dec.unused_data and out == kd["data"] and kd["in_used"] == len(kd["z"]), kd["name"]
+        elif kd["refused"] == -5:
+            assert not dec.eof and out[:len(kd["data"])] == kd["data"], kd["name"]
+        else:
+            assert dec.eof and len(out) == kd["cap"] + 1, kd["name"]
+        if kd["name"].startswith("long_codes/") and kd["name"].endswith("/huff"):       # (literals only: the code is the bytes' own)
+            assert _huffman_max_len(np.bincount(np.frombuffer(kd["data"], dtype=np.uint8), minlength=256).tolist() + [1]) >= 13, kd["name"]
+    assert sum(kd["name"].startswith("long_codes/") for kd in K["deflate"]) == 8
+    assert sum(kd["long"] for kd in K["deflate"]) == 2 and max(kd["cap"] for kd in K["deflate"]) >= 65536
+    for kd in K["lzma"]:
+        z = kd["z"]
+        dec = pylzma.LZMADecompressor(format=pylzma.FORMAT_ALONE)
+        if kd["refused"] == -3:
+            with pytest.raises(pylzma.LZMAError):
+                dec.decompress(z[4:9] + b"\xff" * 8 + z[9:])
+            continue
+        out = dec.decompress(z[4:9] + b"\xff" * 8 + z[9:])
+        if kd["refused"] is None:
+            assert dec.eof and (out if kd["max_out"] < 0 else out[:kd["max_out"]]) == kd["data"] and kd["in_used"] == len(z), kd["name"]
+        elif kd["refused"] == -5:
+            assert not dec.eof and out == kd["data"] and oracle.lzma_zip_decode(z, kd["cap"], -1)[0] == -3, kd["name"]
+        else:
+            assert dec.eof and len(out) == kd["cap"] + 1, kd["name"]
+    assert sum(kd["name"].startswith("lc") and kd["refused"] is None for kd in K["lzma"]) == 8
+    checks = set()
+    for kd in K["xz"]:
+        dec = pylzma.LZMADecompressor(format=pylzma.FORMAT_XZ)
+        if kd["refused"] == -3:
+            with pytest.raises(pylzma.LZMAError):
+                dec.decompress(kd["z"])
+            continue
+        out = dec.decompress(kd["z"])
+        if kd["refused"] is None:
+            assert dec.eof and (out if kd["max_out"] < 0 else out[:kd["max_out"]]) == kd["data"] and kd["in_used"] == len(kd["z"]), kd["name"]
+            checks.add(kd["z"][7])
+        elif kd["refused"] == -5:
+            assert not dec.eof and out[:len(kd["data"])] == kd["data"], kd["name"]
+        else:
+            assert dec.eof and len(out) == kd["cap"] + 1, kd["name"]
+    assert checks == {0, 1, 4, 10}
+    assert any(kd["name"].startswith("multi-block") for kd in K["xz"]) and any("+" in kd["name"] for kd in K["xz"])
+    assert [len(d) for _, d in K["enc"]] == [0, 1, 258, 3000, 2000, 3000, 65536, 70000]
+
+
+def test_inflate_every_ordered_pair(emu, emu_staged):
+    """K1: for every ordered pair (A, B) of the DEFLATE kinds of synth.reuse_kinds() -- good ones from the empty stream to the
+    64 KiB level-9 slice that fills the record caps, and refused ones -- the sequence A, B, A through one wave's LDS slice and
+    record scratch: all three results are the reference's and, to the last byte of the out region, those of the same kind
+    alone on fresh poison.  On the default build and every variant of emu_staged."""
+    kinds = synth.reuse_kinds()["deflate"]
+    for tag, L in zip(("default", "c_caps", "c_short", "c_pool", "c_serial_cl"), [emu] + emu_staged):
+        _every_ordered_pair(_seq_api(L), "deflate", kinds, tag)
+
+
+def _window_walk(L, kd, sizes):
+    """kd's stream alone, window by window (room sizes[k % len] behind at most 32 KiB of history), every window on a fresh
+    wave state -> the windows as entries for _seq, and what each gave"""
+    ents, results = [], []
+    got, state = bytearray(), (0, 0, 0, 0)
+    for k in range(4000):
+        hist = state[2]
+        e = dict(z=kd["z"], cap=hist + sizes[k % len(sizes)], hist=bytes(got[len(got) - hist:]), state=state)
+        r = _seq(L, "deflate", [e], resume=True)[0]
+        st, so = r[0], r[5]
+        assert st in (0, -200), (kd["name"], k, st)
+        valid = r[2] if st == 0 else so[2]
+        assert hist <= valid <= e["cap"]
+        new = r[4][hist:valid]
+        assert r[3] == zlib.crc32(new), (kd["name"], k)
+        ents.append(e)
+        results.append(r)
+        got += new
+        if st == 0:
+            assert bytes(got) == kd["data"], kd["name"]
+            return ents, results
+        assert so[3] & 1
+        state = (so[0], so[1], min(len(got), 32768), 1)
+    raise AssertionError("no end: " + kd["name"])
+
+
+def test_inflate_resume_every_ordered_pair(emu, emu_staged):
+    """K1's resumable kernel: two long kinds cut into windows of 1, 7, 4096 and 32 768 bytes of room (a window too small for
+    the next token stands still and says so), the windows of the two streams interleaved through one wave state in both
+    orders: every window gives what it gave alone on fresh poison -- status, counts, CRC, stop state, every byte of its
+    region -- and the walk alone ended with zlib's bytes."""
+    K = {kd["name"]: kd for kd in synth.reuse_kinds()["deflate"]}
+    a, b = K["text_64k_l9"], K["dist_32768"]
+    for L in [emu] + emu_staged:
+        _seq_api(L)
+        wa, ra = _window_walk(L, a, (1, 7, 4096, 32768))
+        wb, rb = _window_walk(L, b, (7, 4096, 1, 32768))
+        assert len(wa) >= 4 and len(wb) >= 4, (len(wa), len(wb))
+        for first, second in (((wa, ra), (wb, rb)), ((wb, rb), (wa, ra))):
+            ents, want = [], []
+            for k in range(max(len(first[0]), len(second[0]))):
+                for w, r in (first, second):
+                    ents.append(w[k % len(w)])
+                    want.append(r[k % len(w)])
+            got = _seq(L, "deflate", ents, resume=True)
+            for k, (g, w) in enumerate(zip(got, want)):
+                assert g == w, (k, g[:4], w[:4], g[5], w[5])
+
+
+def test_lzma_every_ordered_pair(emu):
+    """K3 as mzhip_lzma_batch runs it: a wave of the slot kernel (one LDS slice, one sprobs) takes A, B, A; what it gives back
+    goes through a wave of the full-model kernel (one LDS slice, one xprobs) in the same order.  lc + lp = 4 behind lc = 0, a
+    given-back entry behind a slot entry, good behind refused: every result is the reference's and the entry's alone."""
+    L = _seq_api(emu)
+    kinds = synth.reuse_kinds()["lzma"]
+    _every_ordered_pair(L, "lzma", kinds, "lzma")
+    # the same through the full-model kernel alone (the launch without a slot kernel, and k_lzma_batch's own loop)
+    emu.emul_lzma_slots.argtypes = emu.emul_lzma.argtypes
+    back = sum(_run(emu.emul_lzma_slots, kd["z"], kd["cap"], C.c_int64(kd["max_out"]), slack_ok=True)[0] == -300 for kd in kinds)
+    assert 3 <= back <= len(kinds) - 3, back         # both paths are in the table
+
+
+def test_xz_every_ordered_pair(emu):
+    """k_xz_batch: container, LZMA2, filters and checks of A, B, A through one mz_xz_lds and one xprobs"""
+    _every_ordered_pair(_seq_api(emu), "xz", synth.reuse_kinds()["xz"], "xz")
+
+
+def _enc_every_ordered_pair(L, fam, ways, parse, back, room, tag):
+    inputs = synth.reuse_kinds()["enc"]
+    ents = [dict(z=d, cap=len(d) + len(d) // 8 + room) for _, d in inputs]
+    alone = [_seq(L, fam, [e], ways=ways, parse=parse)[0] for e in ents]
+    for (name, d), r in zip(inputs, alone):
+        assert r[0] == 0 and r[3] == zlib.crc32(d) and back(r[4][:r[2]]) == d, (tag, name, r[:4])
+    for i in range(len(ents)):
+        for j in range(len(ents)):
+            got = _seq(L, fam, [ents[i], ents[j], ents[i]], ways=ways, parse=parse)
+            for pos, (r, x) in enumerate(zip(got, (i, j, i))):
+                what = (tag, "%s, %s, %s" % (inputs[i][0], inputs[j][0], inputs[i][0]), "entry %d" % pos)
+                d = inputs[x][1]
+                assert r[0] == 0 and r[3] == zlib.crc32(d) and back(r[4][:r[2]]) == d, (what, r[:4])
+                assert r[:4] == alone[x][:4] and r[4] == alone[x][4], (what, "differs from the input coded alone on fresh state")
+
+
+def test_deflate_every_ordered_pair(emu):
+    """K4, each of its three classes: A, B, A through one LDS slice, one token block and one xhead.  zlib inflates every
+    stream back, and the bytes are those of the same input coded alone on fresh poison: deflate_core.h clears its head tables
+    per block, so nothing of an earlier entry may show in a later one's parse."""
+    L = _seq_api(emu)
+    for name, ways, parse in ENC_CLASSES:
+        _enc_every_ordered_pair(L, "k4", ways, parse, lambda z: zlib.decompress(z, -15), 64, name)
+
+
+def test_lzma_encode_every_ordered_pair(emu):
+    """K6's three passes with one wave each: one chain_head table for the chain pass (the 70 000-byte input is the one with
+    more than one block), one head slice and xhead for every block of every entry, one model slice for the range coder.
+    liblzma decodes every stream, and the bytes are those of the same input coded alone on fresh poison (mz_lz_chain and
+    mz_lz_tokenize clear their tables per call, the coder starts every model at 1024: K6 is deterministic in this sense)."""
+    import lzma as pylzma
+
+    L = _seq_api(emu)
+    back = lambda z: pylzma.decompress(z[4:9] + b"\xff" * 8 + z[9:], format=pylzma.FORMAT_ALONE)
+    for ways in (1, 4):
+        _enc_every_ordered_pair(L, "k6", ways, 0, back, 1024, "ways %d" % ways)
