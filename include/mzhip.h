@@ -246,7 +246,8 @@ MZHIP_API int32_t mzhip_deflate_batch(const void *d_in, const uint64_t *d_in_off
  * positions, and a two-position lazy rule (between zlib levels 3 and 6; 3-4x the work); 7..9 = the same candidates and a
  * cost parse over every 64 KiB block (a backward dynamic programme priced with the block's own code lengths: within 3 %
  * of zlib-9's output, 3x the time of level 6 -- as in zlib, the top levels pay for ratio).  window_log2 = 9..15: matches reach at most 2^window_log2 - 262
- * bytes back (zlib's MAX_DIST), so an inflater with that window decodes the stream.  mzhip_deflate_batch == level 1, 15. */
+ * bytes back (zlib's MAX_DIST), so an inflater with that window decodes the stream.  mzhip_deflate_batch == level 1, 15.
+ * (tests/test_gpu_deflate_tokens.py and tests/test_kernel_emul.py test_deflate_window_bound_* measure every distance of every class at every window.) */
 MZHIP_API int32_t mzhip_deflate_batch_level(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
                                       void *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
                                       const uint8_t *d_final, uint32_t n, int32_t level, int32_t window_log2, uint32_t *d_out_len, uint32_t *d_crc,

@@ -539,3 +539,42 @@ def reuse_kinds():
          ("text_70000", c[200000:270000])]
     _REUSE.update(deflate=D, lzma=Z, xz=X, enc=E)
     return _REUSE
+
+
+# ---- encoder inputs that put the window bound, the block choice and the piece framing under load ----------------------
+_ECHO = {}
+
+
+def echo_cases(window_log2):
+    """[(name, data, period)]: inputs for a raw-DEFLATE ENCODER told to keep its matches within 2^window_log2 - 262 bytes
+    (zlib's MAX_DIST, include/mzhip.h).  "echo/P": a seeded random block R of P bytes, R again, and 300 bytes of R a third
+    time (n = 2 P + 300), for P just below, at and just above both 2^w - 262 and 2^w.  R is random, so the only source of the
+    second copy lies exactly P back: an encoder that may take it (P <= 2^w - 262) should, one that may not has literals
+    left.  period = P for these, None for the rest: "text_echo" = 3 x 2^w bytes of the bench corpus (matches at every
+    distance on offer, the far ones tempting), and a run, a short period and two-symbol noise of at most 4 KiB, where a lazy
+    rule and matches handed from one position to the next are busiest.  For w = 15 the largest echo (65 838 bytes) crosses the
+    encoder's 64 KiB block.  Built once per process; nobody changes it."""
+    w = window_log2
+    if w in _ECHO:
+        return _ECHO[w]
+    max_dist = (1 << w) - 262
+    cases = []
+    for k, p in enumerate((max_dist - 1, max_dist, max_dist + 1, (1 << w) - 1, 1 << w, (1 << w) + 1)):
+        r = np.random.RandomState(1000 * w + k).bytes(p)
+        cases.append(("echo/%d" % p, r + r + r[:300], p))
+    text, _ = bench_corpus()
+    cases.append(("text_echo", (text * (3 * (1 << w) // len(text) + 1))[:3 * (1 << w)], None))
+    rnd = np.random.RandomState(1000 * w + 99)
+    cases.append(("run", b"r" * 4096, None))
+    cases.append(("period7", (rnd.bytes(7) * 600)[:4093], None))
+    cases.append(("two_symbols", bytes(rnd.randint(0, 2, size=4095, dtype=np.uint8) + 97), None))
+    _ECHO[w] = cases
+    return cases
+
+
+def incompressible_cases():
+    """[(name, data)]: seeded random bytes of 1, 65535, 65536, 65537 and 131071 bytes: no code shortens them, so a DEFLATE
+    encoder that takes the cheapest block kind stores them, 65535 bytes (the most LEN can say) to a block."""
+    if "noise" not in _ECHO:
+        _ECHO["noise"] = [("noise/%d" % n, np.random.RandomState(7000 + k).bytes(n)) for k, n in enumerate((1, 65535, 65536, 65537, 131071))]
+    return _ECHO["noise"]

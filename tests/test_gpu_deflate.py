@@ -1,4 +1,5 @@
-"""GPU parity tests for K4 (DEFLATE encode, fixed-Huffman blocks, fused CRC-32 of the input) through the C ABI
+"""GPU parity tests for K4 (DEFLATE encode: per 64 KiB block the cheapest of dynamic-Huffman, fixed-Huffman and stored
+coding -- tests/test_gpu_deflate_tokens.py reads the blocks -- with the CRC-32 of the input fused in) through the C ABI
 (mzhip_deflate_batch / mzhip_deflate_host_a) and through the drop-in mz_stream_zlib WRITE path.  Compressor
 output is not a format property, so parity = the reference side (oracle restatement, zlib 1.2.11, the compiled
 reference's mz_stream_zlib READ) inflates the bytes back to the input and every CRC agrees."""

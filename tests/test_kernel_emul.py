@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import oracle
-from tests import synth
+from tests import deflate_tokens, synth
 from tests.test_oracle import _zip_lzma
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -1000,7 +1000,8 @@ def test_deflate_classes_fuzz(emu):
         elif k == 3: d = (c[rnd.randrange(1000):][:rnd.randrange(1, 300)] * 2000)[:n]
         elif k == 4: d = bytes(rnd.choice(b"ab") for _ in range(min(n, 20000)))
         else: d = (bytes(rnd.randrange(256) for _ in range(rnd.randrange(1, 40))) * 70000)[:n]
-        emu.emul_deflate_window(rnd.choice([9, 12, 15, 15]))
+        wlog = rnd.choice([9, 12, 15, 15])
+        emu.emul_deflate_window(wlog)
         a = np.frombuffer(d, dtype=np.uint8).copy() if d else np.zeros(1, np.uint8)
         for name, fn in (("best", emu.emul_deflate_best), ("lazy", emu.emul_deflate_lazy)):
             final = (it + (name == "lazy")) & 1
@@ -1010,6 +1011,9 @@ def test_deflate_classes_fuzz(emu):
             z = out[:ol.value].tobytes()
             back = zlib.decompress(z, -15) if final else zlib.decompressobj(-15).decompress(z)
             assert st == 0 and back == d and crc.value == zlib.crc32(d), (it, name, final, len(d))
+            # zlib at -15 takes any distance up to 32768: the window this case was given is held by the walker
+            m = deflate_tokens.walk(z, open_end=not final).matches
+            assert len(m) == 0 or m[:, 2].max() <= (1 << wlog) - 262, (it, name, final, len(d), wlog, int(m[:, 2].max()))
     emu.emul_deflate_window(15)
 
 
@@ -1074,6 +1078,108 @@ def test_deflate_pieces_with_history(emu):
                 print("%s, %s: 16 KiB pieces with history %.4f, 64 KiB pieces without %.4f, 16 KiB without %.4f" % (
                     name, cls, len(z16) / len(data), len(z64_blind) / len(data), len(z16_blind) / len(data)))
                 assert len(z16) < len(z64_blind) < len(z16_blind)
+
+
+def _deflate_classes(emu):
+    emu.emul_deflate_lazy.argtypes = emu.emul_deflate.argtypes
+    emu.emul_deflate_best.argtypes = emu.emul_deflate.argtypes
+    return (("fast", emu.emul_deflate), ("lazy", emu.emul_deflate_lazy), ("best", emu.emul_deflate_best))
+
+
+def _deflate_fn(fn, d, final, warm=0):
+    """one piece through a class of the emulated encoder between red zones; d = the `warm` bytes in front of the piece + the piece;
+    out_cap is exactly the len + len / 8 + 64 that include/mzhip.h says always suffices -> (status, bytes, crc)"""
+    n = len(d) - warm
+    cap = n + n // 8 + 64
+    g = _Guarded(d, cap)
+    ol, crc = C.c_uint32(), C.c_uint32()
+    st = fn(g.pin, len(d), g.pout, cap, final, C.byref(ol), C.byref(crc))
+    return st, g.check(st, ol.value), crc.value
+
+
+def test_deflate_window_bound_tokens(emu):
+    """include/mzhip.h: "window_log2 = 9..15: matches reach at most 2^window_log2 - 262 bytes back".  Every class of the encoder
+    at every window over synth.echo_cases(w), final and not, read token by token (tests/deflate_tokens.py): no distance beyond
+    the bound -- the fast class's one candidate, the four ways of a bucket, a match handed on to the next positions, the lazy
+    rule's second candidate and the cost parse all keep it -- and, for a random echo whose period the window allows, the echo
+    IS taken at exactly that distance.  Lengths 3 .. 258, block sizes, BFINAL and piece framing are checked on the way
+    (deflate_tokens.check_encoded)."""
+    try:
+        for w in range(9, 16):
+            emu.emul_deflate_window(w)
+            for cname, d, period in synth.echo_cases(w):
+                want = zlib.crc32(d)
+                for cls, fn in _deflate_classes(emu):
+                    for final in (1, 0):
+                        st, z, crc = _deflate_fn(fn, d, final)
+                        assert st == 0 and crc == want, (cls, w, cname, final, st)
+                        deflate_tokens.check_encoded(z, d, w, final, period=period, where=(cls, w, cname, final))
+    finally:
+        emu.emul_deflate_window(15)
+
+
+def test_deflate_window_bound_with_history(emu):
+    """The same bound for a piece that is handed the bytes in front of it (mz_deflate_piece's `warm`, what the WRITE paths do
+    with every piece but a stream's first): the first copy of R lies in the history, the second in the piece, so every
+    match at the echo's distance reaches across the cut.  The history is as long as it takes to hold R, a multiple of 64
+    (random bytes in front of R make it one), and at most the 32 KiB the WRITE paths hand over: the one echo longer than that
+    (w = 15, 2^15 + 1) starts a byte into the piece."""
+    try:
+        for w in range(9, 16):
+            emu.emul_deflate_window(w)
+            for cname, d, period in synth.echo_cases(w):
+                if period is None:
+                    continue
+                pad = -period % 64
+                if pad + period > 32768:
+                    pad = 0
+                warm = min(pad + period, 32768)
+                d = np.random.RandomState(period).bytes(pad) + d
+                hist, piece = d[:warm], d[warm:]
+                want = zlib.crc32(piece)
+                for cls, fn in _deflate_classes(emu):
+                    for final in (1, 0):
+                        emu.emul_deflate_warm(warm)
+                        st, z, crc = _deflate_fn(fn, d, final, warm)
+                        assert st == 0 and crc == want, (cls, w, cname, final, st)
+                        wk = deflate_tokens.check_encoded(z, piece, w, final, prefix=hist, period=period, where=(cls, w, cname, final, warm))
+                        if period <= (1 << w) - 262:        # ... and the first of them starts in the history
+                            m = wk.matches
+                            assert (m[:, 0] < m[:, 2]).any(), (cls, w, cname, final)
+    finally:
+        emu.emul_deflate_warm(0)
+        emu.emul_deflate_window(15)
+
+
+def test_deflate_block_choice_and_framing(emu):
+    """deflate_core.h: "per 64 KiB block the cheapest of dynamic-Huffman / fixed-Huffman / stored coding".  No block of any
+    class, over inputs of every kind, takes more bits than its bytes stored (deflate_tokens.stored_cost_bits: the figure the
+    kernel compares with).  Random bytes are stored: every 64 KiB slice of synth.incompressible_cases() that holds 65535
+    bytes or more comes out as stored blocks of 65535 bytes and the rest (65536 = 65535 + 1) -- a prefix code over 256
+    nearly equally frequent values cannot average below 8 bits (a code of 7 bits costs two of 9) and a header comes on top;
+    a slice of ONE byte is cheaper in a fixed block (19 bits against 48) and must not be stored.  The stream stays
+    within len + len / 8 + 64, and exactly that as out_cap is enough (_deflate_fn gives no more).  Framing: a piece that is
+    not final has BFINAL nowhere and ends on a byte boundary in 00 00 FF FF; a final one has BFINAL on its last block only;
+    the empty final input is the canonical 03 00."""
+    c = synth.corpus()
+    rnd = np.random.RandomState(15)
+    mixed = [("empty", b""), ("one", b"a"), ("abc", b"abc"), ("text_100", c[:100]), ("text_64k", c[:65536]), ("text_64k+1", c[:65537]),
+             ("text_200000", c[:200000]), ("noise_5000", rnd.bytes(5000)), ("noise+text", rnd.bytes(40000) + c[:60000]),
+             ("text+noise+text", c[:70000] + rnd.bytes(65536) + c[:3000]), ("zeros_70000", bytes(70000)), ("run_258", b"z" * 258)]
+    for cls, fn in _deflate_classes(emu):
+        for final in (1, 0):
+            for cname, d in synth.incompressible_cases():
+                st, z, crc = _deflate_fn(fn, d, final)
+                assert st == 0 and crc == zlib.crc32(d), (cls, cname, final, st)
+                assert len(z) <= len(d) + len(d) // 8 + 64
+                wk = deflate_tokens.check_encoded(z, d, 15, final, where=(cls, cname, final))
+                assert len(wk.matches) == 0, (cls, cname, final)
+                deflate_tokens.check_stored_layout(wk, len(d), final, where=(cls, cname, final))
+            for cname, d in mixed + [(n, d) for n, d, _ in synth.echo_cases(12)]:
+                st, z, crc = _deflate_fn(fn, d, final)
+                assert st == 0 and crc == zlib.crc32(d), (cls, cname, final, st)
+                deflate_tokens.check_encoded(z, d, 15, final, where=(cls, cname, final))
+        assert _deflate_fn(fn, b"", 1)[1] == b"\x03\x00", cls
 
 
 def test_emul_bounds_under_asan():
