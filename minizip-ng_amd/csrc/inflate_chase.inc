@@ -138,6 +138,7 @@
     /* a stream whose steps are so short that spans of S bits take more steps than a lane may record (long runs: a
      * 258-byte match can be 2 bits) gets shorter spans from here on -- otherwise every window would throw away what 63
      * of its lanes did */
+    MZ_STAT(23, capped); /* windows whose chain ran into a record cap */
     if (capped && S > 128u) chase_smax = (S >> 1) < 128u ? 128u : (S >> 1);
     /* per-lane tables for the emit (the rings are dead): steps, entry, chase steps, inclusive sums of the group counts */
     PV(uint32_t, gcn);

@@ -48,6 +48,7 @@
 #endif
                 }
                 rm = ln - nf;
+                MZ_STAT(21, (nf != 0u && rm != 0u) ? 1u : 0u); /* a piece split between far and near */
                 en = (en & 0xFFFE0000u) | (si + nf) | ((rm - 1u) << 12); /* what is left (only kept when rm > 0) */
             }
             P(e0) = en;
@@ -124,11 +125,13 @@
         }
         uint64_t U;
         MZ_BALLOT(U, P(rem) != 0u);
+        MZ_STAT_ZERO(11); /* rounds of this batch; 24 = the most a batch took */
         while (U) {
-            MZ_STAT(14, 1);
+            MZ_STAT(14, 1); MZ_STAT(11, 1); MZ_STAT_MAX(24, 11);
             uint64_t R;
             MZ_BALLOT(R, P(rem) != 0u && (P(dep) & U) == 0ull);
             if (!R) { /* cannot happen: the first unfinished piece of the chunk only reads finished bytes */
+                MZ_STAT(22, 1);
                 fail = 1;
                 break;
             }

@@ -49,12 +49,16 @@
 #ifndef MZHIP_INFLATE_CORE_H
 #define MZHIP_INFLATE_CORE_H
 #if defined(MZ_STATS)
-extern unsigned long long mz_stats[24], mz_stat_max;
+extern unsigned long long mz_stats[32], mz_stat_max;
 #define MZ_STAT(i, v) (mz_stats[i] += (v))
+#define MZ_STAT_ZERO(i) (mz_stats[i] = 0)
+#define MZ_STAT_MAX(i, j) (mz_stats[i] = mz_stats[j] > mz_stats[i] ? mz_stats[j] : mz_stats[i]) /* the largest value counter j reached */
 #define MZ_STAT_LANE(v) (mz_stat_max = (v) > mz_stat_max ? (v) : mz_stat_max) /* the slowest lane ... */
 #define MZ_STAT_LANEMAX(i) (mz_stats[i] += mz_stat_max, mz_stat_max = 0)       /* ... is what the wave pays */
 #else
 #define MZ_STAT(i, v) ((void)0)
+#define MZ_STAT_ZERO(i) ((void)0)
+#define MZ_STAT_MAX(i, j) ((void)0)
 #define MZ_STAT_LANE(v) ((void)0)
 #define MZ_STAT_LANEMAX(i) ((void)0)
 #endif

@@ -8,6 +8,8 @@ import zlib
 
 import numpy as np
 
+from tests.token_programs import _DBASE, _DEXT, _LBASE, _LEXT, fixed_stream, stored_blocks  # noqa: F401  (the writers live there now)
+
 
 def corpus():
     import pydoc_data.topics as t
@@ -72,18 +74,6 @@ def deflate_raw(data, level=6, strategy=zlib.Z_DEFAULT_STRATEGY):
     """Exactly the reference writer's parameters (mz_strm_zlib.c:87: raw, 32 KiB window, memLevel 8)."""
     c = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
     return c.compress(data) + c.flush()
-
-
-def stored_blocks(data, block=65535):
-    """A raw DEFLATE stream made of stored blocks only."""
-    out = bytearray()
-    if not data:
-        return bytes([1, 0, 0, 0xFF, 0xFF])
-    for i in range(0, len(data), block):
-        chunk = data[i:i + block]
-        last = 1 if i + block >= len(data) else 0
-        out += bytes([last]) + len(chunk).to_bytes(2, "little") + (len(chunk) ^ 0xFFFF).to_bytes(2, "little") + chunk
-    return bytes(out)
 
 
 def edge_payloads():
@@ -348,54 +338,6 @@ def long_code_payloads(size=200000):
 
 
 # ---- streams made by hand: fixed-Huffman blocks of chosen tokens (zlib never emits distance 32768) ----------------------
-
-_LBASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
-_LEXT = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0]
-_DBASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193,
-          12289, 16385, 24577]
-_DEXT = [0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13]
-
-
-def fixed_stream(tokens):
-    """tokens: int (a literal) or (length, distance) -> one final fixed-Huffman block (RFC 1951 3.2.6)"""
-    acc, nb, out = 0, 0, bytearray()
-
-    def put(v, n):                       # n bits of v, least significant first
-        nonlocal acc, nb
-        acc |= v << nb
-        nb += n
-        while nb >= 8:
-            out.append(acc & 255)
-            acc >>= 8
-            nb -= 8
-
-    def code(v, n):                      # a Huffman code: most significant bit first
-        put(int(format(v, "0%db" % n)[::-1], 2), n)
-
-    def sym(s):
-        if s < 144: code(0x30 + s, 8)
-        elif s < 256: code(0x190 + s - 144, 9)
-        elif s < 280: code(s - 256, 7)
-        else: code(0xC0 + s - 280, 8)
-
-    put(1, 1)
-    put(1, 2)
-    for t in tokens:
-        if isinstance(t, int):
-            sym(t)
-            continue
-        ln, dist = t
-        k = max(i for i in range(29) if _LBASE[i] <= ln) if ln < 258 else 28
-        sym(257 + k)
-        put(ln - _LBASE[k], _LEXT[k])
-        k = max(i for i in range(30) if _DBASE[i] <= dist)
-        code(k, 5)
-        put(dist - _DBASE[k], _DEXT[k])
-    sym(256)
-    if nb:
-        out.append(acc & 255)
-    return bytes(out)
-
 
 def hand_made():
     rnd = np.random.RandomState(21)

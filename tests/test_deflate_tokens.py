@@ -8,6 +8,7 @@ import pytest
 from tests import synth
 from tests.deflate_tokens import DeflateError, stored_cost_bits, walk
 from tests.test_oracle import INCOMPLETE_DISTANCE_SET
+from tests.token_programs import _Bits, _canonical, dynamic_block  # noqa: F401  (the writers live in the token-program helper)
 
 
 def _zlib(z):
@@ -75,63 +76,6 @@ def test_walker_measures_zlibs_window(wbits):
                 assert w.matches[:, 2].max() <= bound, (level, name, int(w.matches[:, 2].max()))
                 far = max(far, int(w.matches[:, 2].max()))
     assert far > bound - 16, (far, bound)
-
-
-class _Bits:
-    def __init__(self):
-        self.acc, self.n, self.out = 0, 0, bytearray()
-
-    def put(self, v, n):                 # n bits of v, least significant first
-        self.acc |= v << self.n
-        self.n += n
-        while self.n >= 8:
-            self.out.append(self.acc & 255)
-            self.acc >>= 8
-            self.n -= 8
-
-    def code(self, v, n):                # a Huffman code: most significant bit first
-        self.put(int(format(v, "0%db" % n)[::-1], 2) if n else 0, n)
-
-    def bytes(self):
-        return bytes(self.out) + (bytes([self.acc]) if self.n else b"")
-
-
-def _canonical(lens):
-    """{symbol: (code, length)} by RFC 1951 3.2.2 (an over-subscribed set still gets numbers: the reader must refuse it)"""
-    codes, code = {}, 0
-    for n in range(1, 16):
-        for s, l in enumerate(lens):
-            if l == n:
-                codes[s] = (code & ((1 << n) - 1), n)
-                code += 1
-        code <<= 1
-    return codes
-
-
-def dynamic_block(lit_lens, dist_lens, tokens, hlit=None):
-    """One final dynamic block with the given code lengths, sent one by one (code-length code: 0 .. 15 in four bits each).
-    tokens: literal / length symbols as ints, a distance as ("d", symbol); extra bits are the caller's: ("x", value, n)."""
-    b = _Bits()
-    b.put(1, 1)
-    b.put(2, 2)
-    nlit = hlit if hlit is not None else max(257, len(lit_lens))
-    lit_lens = list(lit_lens) + [0] * (nlit - len(lit_lens))
-    b.put(nlit - 257, 5)
-    b.put(len(dist_lens) - 1, 5)
-    b.put(19 - 4, 4)
-    for s in (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15):
-        b.put(4 if s < 16 else 0, 3)
-    for l in lit_lens + list(dist_lens):
-        b.code(l, 4)
-    lc, dc = _canonical(lit_lens), _canonical(dist_lens)
-    for t in tokens:
-        if isinstance(t, int):
-            b.code(*lc[t])
-        elif t[0] == "d":
-            b.code(*dc.get(t[1], (t[1], dist_lens[0])))
-        else:
-            b.put(t[1], t[2])
-    return b.bytes()
 
 
 def _lens(pairs, n):
