@@ -226,6 +226,43 @@ MZHIP_API int32_t mzhip_xz_batch(const void *d_in, const uint64_t *d_in_off, con
 MZHIP_API int32_t mzhip_sha_batch(const void *d_buf, const uint64_t *d_off, const uint32_t *d_len, uint32_t n,
                                   uint32_t algorithm, void *d_digest, void *stream);
 
+/* K8: the crypt streams of password-protected entries, read side ------------------------------------------------ */
+
+/* What the reference puts between the archive and the codec of an encrypted entry (mz_zip.c, the use_crypt branch of
+ * mz_zip_entry_open_int), for n entries at once; the decrypted bytes are then an ordinary payload for the codec batches
+ * above.  Entry i reads d_in + d_in_off[i] .. + d_in_len[i] -- the entry's WHOLE compressed size as the central
+ * directory gives it, crypt overhead included -- and writes d_out + d_out_off[i] .. + d_out_len[i]; input and output
+ * must not overlap.  `password` is HOST memory (it travels in the kernel arguments); NULL is MZ_PARAM_ERROR (-102) for
+ * the whole call.  Per-entry status, as the reference's streams answer:
+ *     0     decrypted (and, for AES, authenticated); d_out_len[i] = d_in_len[i] - overhead
+ *   -108    MZ_PASSWORD_ERROR: check byte / verifier differs; nothing is written, d_out_len[i] = 0
+ *   -105    MZ_CRC_ERROR: (AES) the authentication code differs; the decrypted bytes ARE delivered and d_out_len[i] is
+ *           their length, as mz_stream_wzaes_read delivers them before _close finds out (mz_strm_wzaes.c)
+ *   -115    MZ_READ_ERROR: d_in_len[i] is shorter than the overhead; d_out_len[i] = 0
+ *   -102    MZ_PARAM_ERROR: (AES) strength outside 1..3; d_out_len[i] = 0
+ * No byte outside [d_out_off[i], + d_out_len[i]) is written, the input is not changed, and an entry's result does not
+ * depend on its neighbours.  Both read their input at byte granularity (any alignment, nothing outside the entry).
+ * Asynchronous on `stream`.
+ *
+ * mzhip_pkcrypt_batch: PKWARE traditional encryption (mz_strm_pkcrypt.c, APPNOTE 6.1).  Overhead = the 12-byte
+ * encryption header.  d_verify[i]: bits 0-7 = the check byte plain header byte 11 must equal, bits 8-15 = the one for
+ * byte 10, bit 16 = compare byte 10 too (the reference does for version-needed below 2, mz_strm_pkcrypt.c:156-160).  The
+ * check bytes are the CRC's two high bytes, or the DOS time's high and the date's low byte when flag bit 3 is set
+ * (mz_zip_get_pk_verify).  One lane per entry: the key recurrence is serial in the entry's bytes. */
+MZHIP_API int32_t mzhip_pkcrypt_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
+                                      const uint64_t *d_out_off, uint32_t n, const uint8_t *password, uint32_t password_len,
+                                      const uint32_t *d_verify, uint32_t *d_out_len, int32_t *d_status, void *stream);
+/* mzhip_wzaes_batch: WinZip AES, AE-1 and AE-2 alike (mz_strm_wzaes.c).  Entry = salt (4 s + 4 bytes) | verifier (2) |
+ * ciphertext | authentication code (10) with d_strength[i] = s = 1, 2, 3 for AES-128 / 192 / 256, so the overhead is
+ * 4 s + 16.  Key material PBKDF2-HMAC-SHA1(password, salt, 1000 iterations), AES in CTR mode with a little-endian block
+ * counter from 1, HMAC-SHA1 over the ciphertext.  A password longer than 128 bytes (the reference's limit) is
+ * MZ_PARAM_ERROR for the whole call.  Three kernels on `stream`: keys (a lane per PBKDF2 block), CTR (a wave per entry),
+ * authentication (a lane per entry: one entry's HMAC chain is serial, so ONE huge entry is bound by a single lane). */
+MZHIP_API int32_t mzhip_wzaes_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                    const uint8_t *d_strength, void *d_out, const uint64_t *d_out_off, uint32_t n,
+                                    const uint8_t *password, uint32_t password_len, uint32_t *d_out_len, int32_t *d_status,
+                                    void *stream);
+
 /* K4: raw-DEFLATE encode (dynamic / fixed / stored blocks, whichever is cheapest) with fused CRC-32 of the input -- */
 
 /* Replaces, for n pieces at once, mz_stream_zlib_write/_close (mz_strm_zlib.c:203-264,280-305 -> zlib

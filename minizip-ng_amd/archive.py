@@ -23,7 +23,10 @@ _mz = importlib.import_module("minizip-ng_amd")
 COL_METHOD, COL_FLAG, COL_CRC, COL_CSIZE, COL_USIZE, COL_LOCAL, COL_CDPOS, COL_PAYLOAD = range(8)
 MZ_FORMAT_ERROR = -103
 MZ_CRC_ERROR = -105       # mz.h:34
+MZ_PASSWORD_ERROR = -108  # mz.h:37
 MZ_SUPPORT_ERROR = -109   # mz.h:38
+MZ_ZIP_EXTENSION_AES = 0x9901    # mz.h:114
+MZ_COMPRESS_METHOD_AES = 99
 MZ_ZIP_EXTENSION_HASH = 0x1A51   # mz.h:113
 MZ_HASH_SHA1, MZ_HASH_SHA256 = 20, 23   # mz.h:127,131
 
@@ -50,6 +53,50 @@ def hash_fields(buf, table):
                 break
             q += 4 + fsz
     return alg, dsz, dig
+
+
+def crypt_fields(buf, table):
+    """What the crypt streams of encrypted entries need from the central-directory records, per entry:
+    verify u32[n]     mzhip_pkcrypt_batch's word: bits 0-7 the check byte for plain header byte 11, bits 8-15 the one for
+                      byte 10 -- the CRC's two high bytes, or the DOS time's high and the date's low byte when flag bit 3
+                      is set (mz_zip_get_pk_verify, mz_zip.c:192-198) -- bit 16 when version-needed is below 2
+                      (mz_strm_pkcrypt.c:158);
+    aes_version, aes_strength u8[n], method i64[n]   from the 0x9901 extrafield of method-99 entries (7 bytes, version 1
+                      or 2, vendor "AE", strength, the real method; mz_zip.c:415-440), method = the table's otherwise;
+    format_error bool[n]   a method-99 entry without such a field."""
+    a = np.frombuffer(buf, dtype=np.uint8)
+    n = len(table)
+    verify = np.zeros(n, dtype=np.uint32)
+    aes_version = np.zeros(n, dtype=np.uint8)
+    aes_strength = np.zeros(n, dtype=np.uint8)
+    method = np.array(table[:, COL_METHOD], dtype=np.int64)
+    format_error = np.zeros(n, dtype=bool)
+
+    def u16(q):
+        return int(a[q]) | int(a[q + 1]) << 8
+
+    for i in range(n):
+        if not int(table[i, COL_FLAG]) & 1:
+            continue
+        p = int(table[i, COL_CDPOS])
+        need, flag, dos_time, dos_date = u16(p + 6), u16(p + 8), u16(p + 12), u16(p + 14)
+        crc = int(table[i, COL_CRC]) & 0xFFFFFFFF
+        v10, v11 = (dos_date & 255, dos_time >> 8) if flag & 8 else ((crc >> 16) & 255, crc >> 24)
+        verify[i] = v11 | v10 << 8 | (0x10000 if need < 2 else 0)
+        if method[i] != MZ_COMPRESS_METHOD_AES:
+            continue
+        fn, ex = u16(p + 28), u16(p + 30)
+        q, end = p + 46 + fn, p + 46 + fn + ex
+        format_error[i] = True
+        while q + 4 <= end:
+            fid, fsz = u16(q), u16(q + 2)
+            if fid == MZ_ZIP_EXTENSION_AES and q + 4 + fsz <= end:
+                if fsz == 7 and u16(q + 4) in (1, 2) and bytes(a[q + 6:q + 8]) == b"AE":
+                    aes_version[i], aes_strength[i], method[i] = u16(q + 4), a[q + 8], u16(q + 9)
+                    format_error[i] = False
+                break
+            q += 4 + fsz
+    return dict(verify=verify, aes_version=aes_version, aes_strength=aes_strength, method=method, format_error=format_error)
 
 
 def index_bytes(buf):
@@ -119,12 +166,63 @@ class DeviceArchive:
         self.h_file = np.fromfile(path, dtype=np.uint8)
         self.d_file = torch.from_numpy(self.h_file).to(self.device)
 
-    def decode(self, lo=0, hi=None, keep_output=True, verify_hash=False):
+    def _decrypt(self, t, cf, password, stream):
+        """Encrypted entries of the slice -> a device scratch buffer, one call per kind (mzhip_pkcrypt_batch, mzhip_wzaes_batch).
+        Returns (d_scr, scr_off i64[n], plain_len i64[n], crypt_status i32[n]); entries that are not encrypted keep status 0."""
+        import torch
+
+        n = len(t)
+        dev = self.device
+        enc = (t[:, COL_FLAG] & 1) != 0
+        is_aes = enc & (t[:, COL_METHOD] == MZ_COMPRESS_METHOD_AES)
+        cst = np.zeros(n, dtype=np.int32)
+        cst[is_aes & cf["format_error"]] = MZ_FORMAT_ERROR
+        if (t[enc, COL_CSIZE] >= 2**32).any():
+            raise _mz.MzHipError("entries >= 4 GiB are outside the batch path")
+        slot = np.where(enc, (t[:, COL_CSIZE] + 15) // 16 * 16, 0)
+        scr_off = np.zeros(n, dtype=np.int64)
+        if n:
+            np.cumsum(slot[:-1], out=scr_off[1:])
+        d_scr = torch.empty(max(int(slot.sum()), 16), dtype=torch.uint8, device=dev)
+        plain_len = np.zeros(n, dtype=np.int64)
+        L = _mz.lib()
+        pw = bytes(password)
+        for kind, sel in (("pk", np.nonzero(enc & ~is_aes)[0]), ("aes", np.nonzero(is_aes & ~cf["format_error"])[0])):
+            if len(sel) == 0:
+                continue
+            k = len(sel)
+            d_in_off = torch.from_numpy(np.ascontiguousarray(t[sel, COL_PAYLOAD], dtype=np.int64)).to(dev)
+            d_in_len = torch.from_numpy(t[sel, COL_CSIZE].astype(np.uint32).view(np.int32)).to(dev)
+            d_out_off = torch.from_numpy(np.ascontiguousarray(scr_off[sel])).to(dev)
+            r_len, r_st = (torch.zeros(k, dtype=torch.int32, device=dev) for _ in range(2))
+            if kind == "pk":
+                d_ver = torch.from_numpy(cf["verify"][sel].view(np.int32)).to(dev)
+                rc = L.mzhip_pkcrypt_batch(self.d_file.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), d_scr.data_ptr(),
+                                           d_out_off.data_ptr(), k, pw, len(pw), d_ver.data_ptr(), r_len.data_ptr(),
+                                           r_st.data_ptr(), stream)
+            else:
+                d_str = torch.from_numpy(np.ascontiguousarray(cf["aes_strength"][sel])).to(dev)
+                rc = L.mzhip_wzaes_batch(self.d_file.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), d_str.data_ptr(),
+                                         d_scr.data_ptr(), d_out_off.data_ptr(), k, pw, len(pw), r_len.data_ptr(),
+                                         r_st.data_ptr(), stream)
+            if rc != 0:
+                raise _mz.MzHipError("crypt batch failed: %d %s" % (rc, L.mzhip_last_error().decode()))
+            torch.cuda.synchronize()
+            plain_len[sel] = _mz.u32(r_len)
+            cst[sel] = r_st.cpu().numpy()
+        return d_scr, scr_off, plain_len, cst
+
+    def decode(self, lo=0, hi=None, keep_output=True, verify_hash=False, password=None):
         """Decode entries [lo, hi).  Returns dict(crc u32[n], out_len i64[n], status i32[n], ok bool[n],
         out (uint8 CUDA tensor) , out_off i64[n]).  status: 0, MZ_* / zlib-numbered errors, MZ_CRC_ERROR when
         the CRC differs from the central directory, MZ_SUPPORT_ERROR for methods other than 0 / 8 / 14 / 95.
         verify_hash: entries carrying a Hash extrafield are also checked against a device-computed SHA-1 / SHA-256
-        (mismatch -> MZ_CRC_ERROR, other algorithms -> MZ_SUPPORT_ERROR, as mz_zip_reader_entry_open / _close)."""
+        (mismatch -> MZ_CRC_ERROR, other algorithms -> MZ_SUPPORT_ERROR, as mz_zip_reader_entry_open / _close).
+        password (bytes): ZipCrypto and WinZip-AES entries are decrypted on the device into a scratch buffer (one call per
+        kind) and decoded from there by the same per-method launches, AES entries with the real method of their 0x9901
+        field; a crypt status other than 0 (MZ_PASSWORD_ERROR, ...) is the entry's status and its codec is not run.  The
+        CRC is compared for ZipCrypto and AE-1 and skipped for AE-2, whose CRC field is 0 (mz_zip_entry_read_close,
+        mz_zip.c:2116-2128).  Without a password encrypted entries stay MZ_SUPPORT_ERROR."""
         import torch
 
         t = self.table[lo:hi]
@@ -155,74 +253,88 @@ class DeviceArchive:
         def dev_i32(a):
             return torch.from_numpy(np.ascontiguousarray(a).astype(np.int32)).to(dev)
 
+        # where each entry's codec reads its payload: the archive image as it lies in HBM, or -- for entries decrypted just
+        # now -- the scratch buffer, the payload shorter by the crypt overhead ("whole entry consumed" is measured on that)
+        plain = (t[:, COL_FLAG] & 1) == 0
+        meth = np.array(t[:, COL_METHOD], dtype=np.int64)
+        skip_crc = np.zeros(n, dtype=bool)
+        sources = [(self.d_file, plain, np.array(t[:, COL_PAYLOAD], dtype=np.int64), np.array(t[:, COL_CSIZE], dtype=np.int64))]
+        if password is not None and n and not plain.all():
+            cf = crypt_fields(self.h_file, t)
+            with torch.cuda.device(dev):
+                d_scr, scr_off, plain_len, cst = self._decrypt(t, cf, password, stream)
+            meth = cf["method"]
+            skip_crc = ~plain & (cf["aes_version"] == 2)
+            status[~plain & (cst != 0)] = cst[~plain & (cst != 0)]
+            sources.append((d_scr, ~plain & (cst == 0), scr_off, plain_len))
         with torch.cuda.device(dev):
-            # DEFLATE entries of LARGE_ENTRY compressed bytes and more: one wave per entry is 0.1 - 0.2 GB/s, so each of them
-            # is decoded by a wave per DEFLATE block (mzhip_inflate_large, csrc/inflate_parallel.inc), one call per entry
-            large = np.nonzero((t[:, COL_METHOD] == 8) & ((t[:, COL_FLAG] & 1) == 0) & (t[:, COL_CSIZE] >= LARGE_ENTRY))[0]
-            if len(large) and ((t[large, COL_CSIZE] >= 2**32) | (usize[large] >= 2**32)).any():
-                raise _mz.MzHipError("entries >= 4 GiB are outside the batch path")
-            L.mzhip_inflate_large.restype = C.c_int32
-            L.mzhip_inflate_large.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
-            for e in large:
-                ol, iu, ck, st1 = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_int32()
-                rc = L.mzhip_inflate_large(self.d_file.data_ptr() + int(t[e, COL_PAYLOAD]), int(t[e, COL_CSIZE]),
-                                           d_out.data_ptr() + int(out_off[e]), int(usize[e]), C.byref(ol), C.byref(iu), C.byref(ck),
-                                           C.byref(st1), stream)
-                if rc != 0:
-                    raise _mz.MzHipError("mzhip_inflate_large failed: %d %s" % (rc, L.mzhip_last_error().decode()))
-                crc[e], out_len[e] = ck.value, ol.value
-                status[e] = MZ_CRC_ERROR if (st1.value == 0 and iu.value == t[e, COL_CSIZE] and ck.value != np.uint32(t[e, COL_CRC])) else st1.value
-            for method in (8, 14, 95, 0):
-                sel = np.nonzero((t[:, COL_METHOD] == method) & ((t[:, COL_FLAG] & 1) == 0) &
-                                 ~((t[:, COL_METHOD] == 8) & (t[:, COL_CSIZE] >= LARGE_ENTRY)))[0]
-                if len(sel) == 0:
-                    continue
-                k = len(sel)
-                if (t[sel, COL_CSIZE] >= 2**31).any() or (usize[sel] >= 2**31).any():
-                    raise _mz.MzHipError("entries >= 2 GiB are outside the batch path")
-                d_in_off, d_in_len = dev_i64(t[sel, COL_PAYLOAD]), dev_i32(t[sel, COL_CSIZE])
-                d_out_off, d_cap = dev_i64(out_off[sel]), dev_i32(usize[sel])
-                r_len, r_used, r_crc, r_st = (torch.zeros(k, dtype=torch.int32, device=dev) for _ in range(4))
-                if method == 8:
-                    rc = L.mzhip_inflate_batch(self.d_file.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(),
-                                               d_out.data_ptr(), d_out_off.data_ptr(), d_cap.data_ptr(), k,
-                                               r_len.data_ptr(), r_used.data_ptr(), r_crc.data_ptr(), r_st.data_ptr(),
-                                               stream)
-                elif method in (14, 95):
-                    fn = L.mzhip_lzma_batch if method == 14 else L.mzhip_xz_batch
-                    fn.restype = C.c_int32
-                    fn.argtypes = [C.c_void_p] * 7 + [C.c_uint32] + [C.c_void_p] * 5
-                    # TOTAL_OUT_MAX = uncompressed size when the EOS flag is set (mz_zip.c:1833-1846), else none
-                    d_max = dev_i64(np.where(t[sel, COL_FLAG] & 2, usize[sel], -1))
-                    rc = fn(self.d_file.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(),
-                            d_out.data_ptr(), d_out_off.data_ptr(), d_cap.data_ptr(), d_max.data_ptr(),
-                            k, r_len.data_ptr(), r_used.data_ptr(), r_crc.data_ptr(), r_st.data_ptr(), stream)
-                else:   # STORE: the payload IS the data (mz_stream_raw, mz_zip.c:1769); CRC in place, then copy
-                    rc = L.mzhip_crc32_batch(self.d_file.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), k, None,
-                                             r_crc.data_ptr(), stream)
-                    r_len = d_in_len.clone()
-                    r_used = d_in_len.clone()
-                    # a stored entry's two sizes must agree (the slot was sized from the uncompressed one): anything
-                    # else is a format error and nothing is copied for it
-                    same = t[sel, COL_CSIZE] == usize[sel]
-                    r_st = dev_i32(np.where(same, 0, MZ_FORMAT_ERROR))
-                    if keep_output:
-                        for j, e in enumerate(sel):   # host-driven D2D copies: STORE is the CPU-plumbing config
-                            if not same[j]:
-                                continue
-                            c0, cl = int(t[e, COL_PAYLOAD]), int(t[e, COL_CSIZE])
-                            d_out[out_off[e]:out_off[e] + cl] = self.d_file[c0:c0 + cl]
-                if rc != 0:
-                    raise _mz.MzHipError("batch launch failed: %d %s" % (rc, L.mzhip_last_error().decode()))
-                torch.cuda.synchronize()
-                crc[sel] = _mz.u32(r_crc)
-                out_len[sel] = r_len.cpu().numpy()
-                st = r_st.cpu().numpy().astype(np.int32)
-                used = r_used.cpu().numpy().astype(np.int64)
-                # mz_zip_entry_read_close: CRC is verified iff the whole entry was consumed (mz_zip.c:2116-2128)
-                bad_crc = (st == 0) & (used == t[sel, COL_CSIZE]) & (crc[sel] != t[sel, COL_CRC].astype(np.uint32))
-                st[bad_crc] = MZ_CRC_ERROR
-                status[sel] = st
+            for d_src, from_here, p_off, p_len in sources:
+                # DEFLATE entries of LARGE_ENTRY compressed bytes and more: one wave per entry is 0.1 - 0.2 GB/s, so each of them
+                # is decoded by a wave per DEFLATE block (mzhip_inflate_large, csrc/inflate_parallel.inc), one call per entry
+                large = np.nonzero((meth == 8) & from_here & (p_len >= LARGE_ENTRY))[0]
+                if len(large) and ((p_len[large] >= 2**32) | (usize[large] >= 2**32)).any():
+                    raise _mz.MzHipError("entries >= 4 GiB are outside the batch path")
+                L.mzhip_inflate_large.restype = C.c_int32
+                L.mzhip_inflate_large.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
+                for e in large:
+                    ol, iu, ck, st1 = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_int32()
+                    rc = L.mzhip_inflate_large(d_src.data_ptr() + int(p_off[e]), int(p_len[e]),
+                                               d_out.data_ptr() + int(out_off[e]), int(usize[e]), C.byref(ol), C.byref(iu), C.byref(ck),
+                                               C.byref(st1), stream)
+                    if rc != 0:
+                        raise _mz.MzHipError("mzhip_inflate_large failed: %d %s" % (rc, L.mzhip_last_error().decode()))
+                    crc[e], out_len[e] = ck.value, ol.value
+                    status[e] = MZ_CRC_ERROR if (st1.value == 0 and iu.value == p_len[e] and not skip_crc[e] and ck.value != np.uint32(t[e, COL_CRC])) else st1.value
+                for method in (8, 14, 95, 0):
+                    sel = np.nonzero((meth == method) & from_here & ~((meth == 8) & (p_len >= LARGE_ENTRY)))[0]
+                    if len(sel) == 0:
+                        continue
+                    k = len(sel)
+                    if (p_len[sel] >= 2**31).any() or (usize[sel] >= 2**31).any():
+                        raise _mz.MzHipError("entries >= 2 GiB are outside the batch path")
+                    d_in_off, d_in_len = dev_i64(p_off[sel]), dev_i32(p_len[sel])
+                    d_out_off, d_cap = dev_i64(out_off[sel]), dev_i32(usize[sel])
+                    r_len, r_used, r_crc, r_st = (torch.zeros(k, dtype=torch.int32, device=dev) for _ in range(4))
+                    if method == 8:
+                        rc = L.mzhip_inflate_batch(d_src.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(),
+                                                   d_out.data_ptr(), d_out_off.data_ptr(), d_cap.data_ptr(), k,
+                                                   r_len.data_ptr(), r_used.data_ptr(), r_crc.data_ptr(), r_st.data_ptr(),
+                                                   stream)
+                    elif method in (14, 95):
+                        fn = L.mzhip_lzma_batch if method == 14 else L.mzhip_xz_batch
+                        fn.restype = C.c_int32
+                        fn.argtypes = [C.c_void_p] * 7 + [C.c_uint32] + [C.c_void_p] * 5
+                        # TOTAL_OUT_MAX = uncompressed size when the EOS flag is set (mz_zip.c:1833-1846), else none
+                        d_max = dev_i64(np.where(t[sel, COL_FLAG] & 2, usize[sel], -1))
+                        rc = fn(d_src.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(),
+                                d_out.data_ptr(), d_out_off.data_ptr(), d_cap.data_ptr(), d_max.data_ptr(),
+                                k, r_len.data_ptr(), r_used.data_ptr(), r_crc.data_ptr(), r_st.data_ptr(), stream)
+                    else:   # STORE: the payload IS the data (mz_stream_raw, mz_zip.c:1769); CRC in place, then copy
+                        rc = L.mzhip_crc32_batch(d_src.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), k, None,
+                                                 r_crc.data_ptr(), stream)
+                        r_len = d_in_len.clone()
+                        r_used = d_in_len.clone()
+                        # a stored entry's two sizes must agree (the slot was sized from the uncompressed one): anything
+                        # else is a format error and nothing is copied for it
+                        same = p_len[sel] == usize[sel]
+                        r_st = dev_i32(np.where(same, 0, MZ_FORMAT_ERROR))
+                        if keep_output:
+                            for j, e in enumerate(sel):   # host-driven D2D copies: STORE is the CPU-plumbing config
+                                if not same[j]:
+                                    continue
+                                c0, cl = int(p_off[e]), int(p_len[e])
+                                d_out[out_off[e]:out_off[e] + cl] = d_src[c0:c0 + cl]
+                    if rc != 0:
+                        raise _mz.MzHipError("batch launch failed: %d %s" % (rc, L.mzhip_last_error().decode()))
+                    torch.cuda.synchronize()
+                    crc[sel] = _mz.u32(r_crc)
+                    out_len[sel] = r_len.cpu().numpy()
+                    st = r_st.cpu().numpy().astype(np.int32)
+                    used = r_used.cpu().numpy().astype(np.int64)
+                    # mz_zip_entry_read_close: CRC is verified iff the whole entry was consumed (mz_zip.c:2116-2128)
+                    bad_crc = (st == 0) & (used == p_len[sel]) & ~skip_crc[sel] & (crc[sel] != t[sel, COL_CRC].astype(np.uint32))
+                    st[bad_crc] = MZ_CRC_ERROR
+                    status[sel] = st
         if verify_hash and n:
             alg, dsz, dig = hash_fields(self.h_file, t)
             status[(alg != 0) & (alg != MZ_HASH_SHA1) & (alg != MZ_HASH_SHA256) & (status == 0)] = MZ_SUPPORT_ERROR

@@ -131,6 +131,61 @@ MZ_DEV void mz_sha1_run(const uint8_t *p, uint64_t n, uint32_t h[5]) {
     }
 }
 
+/* One SHA-1 compression: h += rounds(h, w).  w[] is the block as 16 big-endian words and is used up as the schedule
+ * window.  (mz_sha1_run above keeps its own copy of the rounds: its code is what k_sha_batch<20> was measured with.) */
+MZ_DEV void mz_sha1_block(uint32_t h[5], uint32_t w[16]) {
+    uint32_t a = h[0], bb = h[1], c = h[2], d = h[3], e = h[4];
+#pragma unroll
+    for (int i = 0; i < 80; i++) {
+        if (i >= 16) {
+            const uint32_t x = w[(i - 3) & 15] ^ w[(i - 8) & 15] ^ w[(i - 14) & 15] ^ w[i & 15];
+            w[i & 15] = MZ_ROR32(x, 31);
+        }
+        uint32_t f, k;
+        if (i < 20) { f = (bb & c) | (~bb & d); k = 0x5A827999; }
+        else if (i < 40) { f = bb ^ c ^ d; k = 0x6ED9EBA1; }
+        else if (i < 60) { f = (bb & c) | (bb & d) | (c & d); k = 0x8F1BBCDC; }
+        else { f = bb ^ c ^ d; k = 0xCA62C1D6; }
+        const uint32_t t = MZ_ROR32(a, 27) + f + e + k + w[i & 15];
+        e = d; d = c; c = MZ_ROR32(bb, 2); bb = a; a = t;
+    }
+    h[0] += a; h[1] += bb; h[2] += c; h[3] += d; h[4] += e;
+}
+
+MZ_DEV void mz_sha1_iv(uint32_t h[5]) {
+    h[0] = 0x67452301; h[1] = 0xEFCDAB89; h[2] = 0x98BADCFE; h[3] = 0x10325476; h[4] = 0xC3D2E1F0;
+}
+
+/* SHA-1 taken up in the middle: h[] is the state after `prefix` bytes (a multiple of 64) that the caller hashed before;
+ * p[0 .. n) is the rest of the message.  On return h[] holds the digest words of prefix || p.  HMAC's two passes start
+ * from the states of the padded key block (crypt_core.h), so a message costs no compression of the key. */
+MZ_DEV void mz_sha1_resume(const uint8_t *p, uint64_t n, uint32_t h[5], uint64_t prefix) {
+    const uint64_t blocks = (n + 9 + 63) / 64, total_words = blocks * 16, full = n / 64, bits = (prefix + n) << 3;
+    for (uint64_t b = 0; b < blocks; b++) {
+        uint32_t w[16];
+        if (b < full) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                uint32_t q[4];
+                __builtin_memcpy(q, p + 64 * b + 16 * (uint64_t)i, 16);
+                w[4 * i] = __builtin_bswap32(q[0]);
+                w[4 * i + 1] = __builtin_bswap32(q[1]);
+                w[4 * i + 2] = __builtin_bswap32(q[2]);
+                w[4 * i + 3] = __builtin_bswap32(q[3]);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const uint64_t wi = b * 16 + (uint64_t)i;
+                /* the two length words count the prefix too; everything else is mz_sha_word's padding of p alone */
+                w[i] = wi == total_words - 1 ? (uint32_t)bits : wi == total_words - 2 ? (uint32_t)(bits >> 32)
+                                                                                      : mz_sha_word(p, n, 0, wi);
+            }
+        }
+        mz_sha1_block(h, w);
+    }
+}
+
 /* ---- SHA-512 / SHA-384 (FIPS 180-4): 128-byte blocks, 80 rounds on 64-bit words ---------------------------- */
 MZ_CONST_TABLE uint64_t mz_k512[80] = {
     0x428a2f98d728ae22ull, 0x7137449123ef65cdull, 0xb5c0fbcfec4d3b2full, 0xe9b5dba58189dbbcull,

@@ -39,6 +39,7 @@
 #include "adler32_core.h"
 #include "xz_core.h"
 #include "lzma_enc_core.h"
+#include "crypt_core.h"
 
 #ifndef MZ_WAVES_PER_WG
 #define MZ_WAVES_PER_WG 4
@@ -395,6 +396,107 @@ __global__ __launch_bounds__(256, 4) void k_sha_batch(ShaArgs a) {
     }
     uint32_t *d = (uint32_t *)(a.digest + (size_t)e * 32);
     for (uint32_t i = 0; i < 8; i++) d[i] = i < words ? __builtin_bswap32(h[i]) : 0u;
+}
+
+// K8: the crypt streams of password-protected entries, read side (crypt_core.h).
+struct PkcryptArgs {
+    const uint8_t *in;
+    const uint64_t *in_off;
+    const uint32_t *in_len;
+    uint8_t *out;
+    const uint64_t *out_off;
+    uint32_t n;
+    uint32_t k0, k1, k2;    // the three keys after the password (host: mz_pk_init_keys_host)
+    const uint32_t *verify; // per entry: check bytes and whether byte 10 counts, see mzhip_pkcrypt_batch
+    uint32_t *out_len;
+    int32_t *status;
+    const mzhip_crc_tables *tabs;
+};
+
+// ZipCrypto: the key recurrence is serial in an entry's bytes, so ONE LANE decrypts one entry (64 per wave).
+__global__ __launch_bounds__(256) void k_pkcrypt_batch(PkcryptArgs a) {
+    __shared__ uint32_t crc_tab[256];
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) crc_tab[i] = a.tabs->byte_tab[i];
+    __syncthreads();
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.n) return;
+    uint32_t out_len;
+    a.status[e] = mz_pkcrypt_entry(a.in + a.in_off[e], a.in_len[e], a.out + a.out_off[e], a.verify[e], a.k0, a.k1, a.k2, crc_tab,
+                                   &out_len);
+    a.out_len[e] = out_len;
+}
+
+struct WzaesArgs {
+    const uint8_t *in;
+    const uint64_t *in_off;
+    const uint32_t *in_len;
+    const uint8_t *strength;
+    uint8_t *out;
+    const uint64_t *out_off;
+    uint32_t n;
+    uint32_t password_len;
+    uint8_t password[MZ_WZAES_PW_MAX];
+    uint32_t *out_len;
+    int32_t *status;
+    uint32_t *counter;
+    mz_wzaes_entry_keys *keys; // n records of scratch
+};
+
+// Key derivation: one lane per (entry, PBKDF2 block) -- four lane slots per entry, of which 2, 3 or 4 work -- then, behind a
+// workgroup barrier (an entry's slots sit in one workgroup), the slot-0 lane checks the verifier, expands the AES key and
+// leaves the HMAC pad states.  No lane leaves before the barrier.
+__global__ __launch_bounds__(256) void k_wzaes_keys(WzaesArgs a) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, e = t >> 2, b = t & 3u;
+    const bool live = e < a.n;
+    const uint8_t *in = nullptr;
+    uint32_t in_len = 0, strength = 0;
+    if (live) {
+        in = a.in + a.in_off[e];
+        in_len = a.in_len[e];
+        strength = a.strength[e];
+        mz_hmac_sha1_key pw;
+        mz_hmac_sha1_init(&pw, a.password, a.password_len);
+        mz_wzaes_km_block(&pw, in, in_len, strength, b, a.keys + e);
+    }
+    __syncthreads(); // the km bytes of the entry's other slots (global memory, workgroup scope)
+    if (live && b == 0) {
+        uint32_t out_len;
+        a.status[e] = mz_wzaes_finish_keys(in, in_len, strength, a.keys + e, &out_len);
+        a.out_len[e] = out_len;
+    }
+}
+
+// AES-CTR: one wave per entry on a persistent grid; round keys and counters base are wave-uniform, lane l of a pass owns
+// the 16-byte block 64 i + l, so a pass reads and writes a contiguous 1 KiB.  Entries whose key step failed are skipped.
+__global__ __launch_bounds__(MZ_WAVES_PER_WG * 64) void k_wzaes_ctr(WzaesArgs a) {
+    __shared__ mz_aes_tables tab;
+    for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) mz_aes_table_entry(&tab, i);
+    __syncthreads();
+    MZ_LANE_DECL
+    for (;;) {
+        uint32_t e;
+        MZ_WAVE_FETCH_ADD(e, a.counter);
+        if (e >= a.n) break;
+        const mz_wzaes_entry_keys *ek = a.keys + e;
+        if (MZ_UNIFORM((uint32_t)ek->status) != 0u) continue;
+        const uint32_t strength = MZ_UNIFORM((uint32_t)a.strength[e]), sl = mz_wzaes_salt_len(strength);
+        const uint32_t n = MZ_UNIFORM(a.in_len[e]) - sl - MZ_WZAES_VERIFY - MZ_WZAES_AUTH;
+        const uint64_t io = a.in_off[e], oo = a.out_off[e];
+        const uint8_t *in = a.in + (((uint64_t)MZ_UNIFORM((uint32_t)(io >> 32)) << 32) | MZ_UNIFORM((uint32_t)io));
+        uint8_t *out = a.out + (((uint64_t)MZ_UNIFORM((uint32_t)(oo >> 32)) << 32) | MZ_UNIFORM((uint32_t)oo));
+        mz_wzaes_ctr(in + sl + MZ_WZAES_VERIFY, n, out, ek->rk, MZ_UNIFORM(ek->rounds), &tab);
+    }
+}
+
+// Authentication: HMAC-SHA1 over the ciphertext is one serial chain per entry -- one lane per entry, like k_sha_batch<20>.
+// It reads the input only, so it may run before or behind the CTR kernel.
+__global__ __launch_bounds__(256, 4) void k_wzaes_auth(WzaesArgs a) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.n) return;
+    const mz_wzaes_entry_keys *ek = a.keys + e;
+    if (ek->status != 0) return;
+    const int32_t st = mz_wzaes_auth(a.in + a.in_off[e], a.in_len[e], a.strength[e], ek);
+    if (st != 0) a.status[e] = st;
 }
 
 struct DeflateArgs {
