@@ -99,6 +99,22 @@ typedef struct mz_lzma_state {
 #define LZ_PRIO_BULK() ((void)0)
 #endif
 
+/* LZ_STAT: counters of an MZ_LZ_STATS build of the host emulation (tests/test_lzma_packets.py holds its packet programs to
+ * what they are named for with them); nothing in every other build.  0 swaps of the slot build, 1 entries it gave back, 2
+ * decisions through LZ_BIT_X, 3 / 4 matched / plain literals in the upper half of an lc + lp = 4 model, 5 .. 13 matched
+ * literals by the bit position at which they left the match tree (13: never), 14 refills of the input window, 15 match copies
+ * cut at out_cap, 16 .. 21 LZMA2 chunks by control class (1, 2, 0x80, 0xA0, 0xC0, 0xE0), 22 stops of the resumable builds
+ * in front of a packet, 23 the output position of the last swap, 24 other control bytes */
+#if defined(MZ_LZ_STATS) && defined(MZHIP_HOST_EMUL)
+static uint64_t mz_lz_stats[32];
+#define LZ_STAT(i, v) (mz_lz_stats[i] += (v))
+#define LZ_STAT_SET(i, v) (mz_lz_stats[i] = (v))
+#define LZ_STAT_BITS(x) (31u - (uint32_t)__builtin_clz(x)) /* bits decoded into a symbol that started at 1 */
+#else
+#define LZ_STAT(i, v) ((void)0)
+#define LZ_STAT_SET(i, v) ((void)0)
+#endif
+
 typedef struct mz_lzma_result {
     int32_t status;
     uint32_t out_len;
@@ -127,6 +143,7 @@ typedef struct mz_lzma_result {
             if (in_pos - in_base >= 256u) {                                             \
                 in_base = in_pos;                                                       \
                 LZ_REFILL();                                                            \
+                LZ_STAT(14, 1);                                                         \
             }                                                                           \
             uint32_t _rel = in_pos - in_base;                                           \
             uint32_t _dw = LZ_WIN_DW(_rel >> 2);                                        \
@@ -177,6 +194,7 @@ typedef struct mz_lzma_result {
     do {                                                                                \
         LZ_NORM();                                                                      \
         uint32_t _pi = (idx) - LZ_NUM_PROBS;                                            \
+        LZ_STAT(2, 1);                                                                  \
         uint32_t _p = LZ_U(prx[_pi]);                                                   \
         uint32_t _bound = (range >> 11) * _p;                                           \
         uint32_t _diff;                                                                 \
@@ -307,8 +325,12 @@ MZ_DEV uint32_t mz_prob_half(uint32_t pair, uint32_t b) { return (pair >> (b << 
                 uint32_t b;                                                             \
                 LZ_BIT_P(b, lbase + ((1u + mbit) << 8) + sym, _pv);                     \
                 sym = (sym << 1) | b;                                                   \
-                if (sym >= 0x100u) break;                                               \
+                if (sym >= 0x100u) {                                                    \
+                    LZ_STAT(mbit != b ? 12 : 13, 1);                                    \
+                    break;                                                              \
+                }                                                                       \
                 if (mbit != b) {                                                        \
+                    LZ_STAT(4 + LZ_STAT_BITS(sym), 1);                                  \
                     _pv = mz_prob_half(_pp, b);                                      \
                     _plain = 2;                                                         \
                     break;                                                              \
@@ -365,7 +387,11 @@ MZ_DEV uint32_t mz_prob_half(uint32_t pair, uint32_t b) { return (pair >> (b << 
                 uint32_t b;                                                             \
                 BITM(b, lbase + ((1u + mbit) << 8) + sym);                              \
                 sym = (sym << 1) | b;                                                   \
-                if (mbit != b) break;                                                   \
+                if (mbit != b) {                                                        \
+                    LZ_STAT(4 + LZ_STAT_BITS(sym), 1);                                  \
+                    break;                                                              \
+                }                                                                       \
+                if (sym >= 0x100) LZ_STAT(13, 1);                                       \
             } while (sym < 0x100);                                                      \
         }                                                                               \
         while (sym < 0x100) {                                                           \
@@ -383,6 +409,7 @@ MZ_DEV uint32_t mz_prob_half(uint32_t pair, uint32_t b) { return (pair >> (b << 
         if (lbase < LZ_NUM_PROBS) {                                                                                   \
             LZ_LITERAL_PF();                                                                                          \
         } else { /* lc + lp = 4, upper half of the literal model */                                                   \
+            LZ_STAT(state >= 7 ? 3 : 4, 1);                                                                           \
             LZ_LITERAL(LZ_BIT_X);                                                                                     \
         }                                                                                                             \
     } while (0)
@@ -435,7 +462,10 @@ MZ_DEV uint32_t mz_prob_half(uint32_t pair, uint32_t b) { return (pair >> (b << 
                 }                                                                                                     \
             }                                                                                                         \
             MZ_WAVE_SYNC();                                                                                           \
+            LZ_STAT(0, 1);                                                                                            \
+            LZ_STAT_SET(23, opos);                                                                                    \
             if (++sswaps > 64u + (opos >> 7)) { /* more than a swap per 128 bytes: not this kernel's data */          \
+                LZ_STAT(1, 1);                                                                                        \
                 status = MZHIP_RETRY;                                                                                 \
                 goto finish;                                                                                          \
             }                                                                                                         \
@@ -573,6 +603,7 @@ MZ_DEV uint32_t mz_prob_half(uint32_t pair, uint32_t b) { return (pair >> (b << 
             if (n > out_cap - opos) {                                                                                 \
                 n = out_cap - opos;                                                                                   \
                 full = 1;                                                                                             \
+                LZ_STAT(15, 1);                                                                                       \
             }                                                                                                         \
             LZ_PRIO_BULK();                                                                                           \
             const uint32_t dist = rep0 + 1;                                                                           \
@@ -691,6 +722,7 @@ MZ_DEV uint32_t mz_prob_half(uint32_t pair, uint32_t b) { return (pair >> (b << 
 #define LZ_RESUME_CHECK()                                                                                   \
     if (st && (opos + 274u > out_cap || (!last_input && in_pos + 64u > rc_len))) {                          \
         status = (opos + 274u > out_cap) ? MZHIP_OUT_FULL : MZHIP_BUF_ERROR;                                \
+        LZ_STAT(22, 1);                                                                                     \
         goto stop_here;                                                                                     \
     }
 #pragma push_macro("LZ_CRC_LIMIT")

@@ -430,6 +430,7 @@ MZ_DEV void mz_xz_entry(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32
                 const uint32_t ctl = XZ_BYTE(pos);
                 pos++;
                 if (ctl == 0) break;
+                LZ_STAT(ctl < 0x80 ? (ctl <= 2 ? 15 + ctl : 24) : 18 + ((ctl >> 5) & 3), 1);
                 if (ctl >= 0xE0 || ctl == 1) {
                     need_props = 1;
                     need_dict_reset = 0;
@@ -772,6 +773,7 @@ MZ_DEV void mz_lzma2_run(const uint8_t *in, uint32_t in_len, uint8_t *out, uint3
                 goto finish;
             }
             const uint32_t resets_dict = (ctl >= 0xE0 || ctl == 1) ? 1u : 0u;
+            LZ_STAT(ctl < 0x80 ? (ctl <= 2 ? 15 + ctl : 24) : 18 + ((ctl >> 5) & 3), 1);
             if (!resets_dict && need_dict_reset) goto finish;
             if (ctl < 0x80) {
                 if (ctl > 2) goto finish;

@@ -425,6 +425,15 @@ extern "C" int32_t emul_lzma_resume(const uint8_t *in, uint32_t in_len, uint8_t 
     *in_used = r.in_used;
     return r.status;
 }
+#if defined(MZ_LZ_STATS)
+/* the counters of lzma_core.h's LZ_STAT: copies the 32 of them out and, if asked, sets them to zero */
+extern "C" void emul_lz_stats(uint64_t *out, int reset) {
+    for (int i = 0; i < 32; i++) {
+        out[i] = mz_lz_stats[i];
+        if (reset) mz_lz_stats[i] = 0;
+    }
+}
+#endif
 extern "C" uint32_t emul_lzma_slots_lds_bytes(void) { return (uint32_t)sizeof(mz_lzma_lds_s); }
 extern "C" uint32_t emul_lzma_lds_bytes(void) { return (uint32_t)sizeof(mz_lzma_lds); }
 
