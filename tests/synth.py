@@ -320,10 +320,11 @@ def xz_filter_cases():
 
 
 def long_code_payloads(size=200000):
-    """(name, data, raw_deflate): streams whose dynamic Huffman codes reach 13-15 bits and use many symbols, so the
-    decoder's second-level literal/length tables are exercised up to their capacity (zlib Z_HUFFMAN_ONLY / level 9 on
-    data with geometric byte statistics, all 256 byte values present).  size: bytes drawn (the rare symbols are the 512
-    bytes behind them, so the code lengths stay as long at a tenth of the default)."""
+    """(name, data, raw_deflate): streams whose dynamic Huffman codes reach 13-15 bits and use many symbols: long codes
+    from zlib's own Huffman construction (zlib Z_HUFFMAN_ONLY / level 9 on data with geometric byte statistics, all 256
+    byte values present), which fill a fraction of the decoder's second-level literal/length table -- the code that fills
+    it to its capacity is in the `sets` family of tests/header_programs.py.  size: bytes drawn (the rare symbols are the
+    512 bytes behind them, so the code lengths stay as long at a tenth of the default)."""
     out = []
     for seed, ratio in ((1, 0.5), (2, 0.6), (3, 0.7), (4, 0.8)):
         rnd = np.random.RandomState(seed)

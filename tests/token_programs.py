@@ -19,6 +19,8 @@ A PROGRAM is a list of blocks.  A block is (kind, tokens, final) or (kind, token
              dshape / done / ddeep / dlens the same for the distance code, rle = send the code lengths with the repeat
              codes 16, 17 and 18 and a Huffman code-length code (default: one by one, four bits each, as dynamic_block
              does), hlit / hdist = header fields to send (trailing zeros make up the difference).
+             hdr = a header program (tests/header_programs.py): the header spelled field by field and sent verbatim in
+             place of all of the above; the tokens are coded with the two codes its operations spell.
 
 encode(program) writes the stream, expand(program) is the plain statement of what it stands for, tokens_of(program) what
 a token walker must read back.  The families at the end return (name, program) lists from a seed."""
@@ -286,6 +288,42 @@ def _send_lengths(b, lit_lens, dist_lens, rle):
         b.put(x, nx)
 
 
+_CL_EXTRA = {16: (2, 3), 17: (3, 3), 18: (7, 11)}     # repeat code: (extra bits, shortest run)
+
+
+def spelled_lengths(hdr):
+    """(literal / length code lengths, distance code lengths) the operations of a header program spell, None where they
+    spell none: a 16 with nothing before it, or not exactly HLIT + 257 + HDIST + 1 lengths.  Nothing else is judged."""
+    nlen, seq = hdr["hlit"] + 257, []
+    for s, x in hdr["ops"]:
+        if s < 16:
+            seq.append(s)
+        elif s == 16 and not seq:
+            return None
+        else:
+            seq += [seq[-1] if s == 16 else 0] * (_CL_EXTRA[s][1] + x)
+    if len(seq) != nlen + hdr["hdist"] + 1:
+        return None
+    return seq[:nlen], seq[nlen:]
+
+
+def _send_header(b, hdr):
+    """a header program, verbatim: the raw HLIT, HDIST and HCLEN fields, hclen + 4 lengths of the code-length code in the
+    order of transmission, the operations (symbol, extra value) through that code, then hdr["raw"] = [(value, bits)]"""
+    b.put(hdr["hlit"], 5)
+    b.put(hdr["hdist"], 5)
+    b.put(hdr["hclen"], 4)
+    for s in _CL_ORDER[:hdr["hclen"] + 4]:
+        b.put(hdr["cl"][s], 3)
+    codes = _reversed_codes(hdr["cl"])
+    for s, x in hdr["ops"]:
+        b.put(*codes[s])
+        if s >= 16:
+            b.put(x, _CL_EXTRA[s][0])
+    for v, n in hdr.get("raw", ()):
+        b.put(v, n)
+
+
 def _reversed_codes(lens):
     return {s: (int(format(c, "0%db" % n)[::-1], 2), n) for s, (c, n) in _canonical(lens).items()}
 
@@ -307,13 +345,15 @@ def block_lengths(tokens, opts):
     return lit[:nl], dist[:nd]
 
 
-def encode(program):
-    """the raw DEFLATE stream of a program"""
+def encode(program, marks=None):
+    """the raw DEFLATE stream of a program (marks: a list that receives the bit position of every block's first bit)"""
     b = _Bits()
     put = b.put
     for blk in program:
         kind, tokens, final = blk[0], blk[1], blk[2]
-        opts = blk[3] if len(blk) > 3 else {}
+        opts = (blk[3] if len(blk) > 3 else None) or {}
+        if marks is not None:
+            marks.append(8 * len(b.out) + b.n)
         put(1 if final else 0, 1)
         if kind == "stored":
             put(0, 2)
@@ -328,8 +368,15 @@ def encode(program):
         else:
             assert kind == "dynamic", kind
             put(2, 2)
-            lit, dist = block_lengths(tokens, opts)
-            _send_lengths(b, lit, dist, opts.get("rle", False))
+            if "hdr" in opts:
+                _send_header(b, opts["hdr"])
+                lit, dist = spelled_lengths(opts["hdr"]) or ([], [])
+                if 256 not in _canonical(lit):       # (a header without an end-of-block code is refused: nothing follows it)
+                    assert not tokens
+                    continue
+            else:
+                lit, dist = block_lengths(tokens, opts)
+                _send_lengths(b, lit, dist, opts.get("rle", False))
             lc, dc = _reversed_codes(lit), _reversed_codes(dist)
         for t in tokens:
             if isinstance(t, int):
