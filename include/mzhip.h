@@ -263,6 +263,35 @@ MZHIP_API int32_t mzhip_wzaes_batch(const void *d_in, const uint64_t *d_in_off, 
                                     const uint8_t *password, uint32_t password_len, uint32_t *d_out_len, int32_t *d_status,
                                     void *stream);
 
+/* K8, the write side: what mz_stream_pkcrypt_write / mz_stream_wzaes_write (and _open / _close in write mode) put between
+ * the codec and the archive, for n entries at once.  Entry i reads the (compressed) plain payload d_in + d_in_off[i] ..
+ * + d_in_len[i] and WRITES exactly [d_out_off[i], d_out_off[i] + d_out_len[i]) of d_out plus element i of d_out_len and
+ * d_status, nothing else; the input is unchanged; input and output must not overlap; both sides work at any byte
+ * alignment; an entry's result does not depend on its neighbours.  The CALLER supplies the randomness (the library has no
+ * entropy source, and given those bytes the output is fully determined).  `password` is HOST memory; NULL is
+ * MZ_PARAM_ERROR (-102) for the whole call; n = 0 returns 0 and touches nothing.  Per-entry status:
+ *     0     encrypted; d_out_len[i] = d_in_len[i] + overhead
+ *   -102    MZ_PARAM_ERROR: (AES) strength outside 1..3, or a d_in_len[i] whose d_out_len[i] would not fit 32 bits;
+ *           d_out_len[i] = 0 and not a byte of the entry's output is written
+ * Asynchronous on `stream`.
+ *
+ * mzhip_pkcrypt_encrypt_batch: overhead = the 12-byte encryption header in front of the payload.  d_header + 10 i = the ten
+ * free (random) bytes of entry i's header; d_verify[i] as on the read side: bits 8-15 become plain header byte 10, bits 0-7
+ * byte 11 (bit 16 is ignored) -- the CRC's two high bytes when no data descriptor is written.  One lane per entry. */
+MZHIP_API int32_t mzhip_pkcrypt_encrypt_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
+                                              const uint64_t *d_out_off, uint32_t n, const uint8_t *password, uint32_t password_len,
+                                              const uint32_t *d_verify, const uint8_t *d_header, uint32_t *d_out_len, int32_t *d_status,
+                                              void *stream);
+/* mzhip_wzaes_encrypt_batch: entry = salt (4 s + 4) | verifier (2) | ciphertext | authentication code (10), overhead
+ * 4 s + 16, s = d_strength[i].  d_salt + 16 i = a 16-byte record of which the first 4 s + 4 bytes are entry i's salt.  A
+ * password longer than 128 bytes is MZ_PARAM_ERROR for the whole call.  Three kernels on `stream`: keys (writes salt and
+ * verifier), CTR (writes the ciphertext), authentication -- which reads the ciphertext the CTR kernel WROTE and is
+ * therefore ordered behind it (on the read side the two are independent); it alone writes the last 10 bytes. */
+MZHIP_API int32_t mzhip_wzaes_encrypt_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                            const uint8_t *d_strength, const uint8_t *d_salt, void *d_out, const uint64_t *d_out_off,
+                                            uint32_t n, const uint8_t *password, uint32_t password_len, uint32_t *d_out_len,
+                                            int32_t *d_status, void *stream);
+
 /* K4: raw-DEFLATE encode (dynamic / fixed / stored blocks, whichever is cheapest) with fused CRC-32 of the input -- */
 
 /* Replaces, for n pieces at once, mz_stream_zlib_write/_close (mz_strm_zlib.c:203-264,280-305 -> zlib

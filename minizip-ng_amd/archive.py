@@ -10,6 +10,9 @@ mz_zip_reader_entry_open / _close do it on the CPU in a crypto build (mz_zip_rw.
 
 Sharding: entries are independent, so ranks take contiguous slices of the entry table balanced by
 compressed+uncompressed bytes; the only collective is the gather of the per-entry {crc, out_len, status} words.
+
+The writer (encode_archive, at the end): one codec launch, one encrypt call (ZipCrypto / WinZip AES) and one copy back per
+archive, the ZIP32 container assembled on the host (assemble_archive).
 """
 import ctypes as C
 import importlib
@@ -362,3 +365,177 @@ class DeviceArchive:
         ok = (status == 0) & (out_len == usize)
         return dict(crc=crc, out_len=out_len, status=status, ok=ok, out=d_out if keep_output else None,
                     out_off=out_off)
+
+
+# ---- the writer: compress -> encrypt -> container --------------------------------------------------------------------------
+
+ZIP32_MAX = 0xFFFFFFFF        # a size or offset field holding this value announces ZIP64, which is not written
+ZIP32_MAX_ENTRIES = 0xFFFF    # ... and so does an entry count of 65 535: the largest count written is 65 534
+
+
+def crypt_overhead(kind, strength=3):
+    """bytes the crypt stream adds to an entry's payload: 12 (ZipCrypto), 4 s + 16 (WinZip AES), 0"""
+    return 0 if kind is None else 12 if kind == "pk" else 4 * strength + 16
+
+
+def _check_writer_args(n, method, kind, strength, ae_version):
+    if method not in (0, 8, 14):
+        raise _mz.MzHipError("encode_archive writes methods 0, 8 and 14, not %r" % (method,))
+    if kind not in (None, "pk", "aes"):
+        raise _mz.MzHipError("kind is None, 'pk' or 'aes', not %r" % (kind,))
+    if kind == "aes" and (strength not in (1, 2, 3) or ae_version not in (1, 2)):
+        raise _mz.MzHipError("WinZip AES: strength 1..3 and AE-1 or AE-2")
+    if n >= ZIP32_MAX_ENTRIES:
+        raise _mz.MzHipError("%d entries need ZIP64, which is not written" % n)
+
+
+def assemble_archive(names, payloads, crcs, usizes, method=8, kind=None, strength=3, ae_version=2, mtime=None):
+    """The host side of encode_archive: local headers, the central directory and one end record around payloads that are
+    already what the archive stores (compressed with `method`, then encrypted as `kind` says: mz_zip_entry_write_header,
+    mz_zip.c).  crcs / usizes: CRC-32 and length of the plain data.  No data descriptor is written (sizes and CRCs are
+    known before any header is), so flag bit 3 stays clear and ZipCrypto's check bytes are the CRC's two high bytes.  AES
+    entries are method 99 with the 7-byte 0x9901 field (version, "AE", strength, the real method) in both headers, version
+    needed 51, and -- AE-2 -- CRC 0.  Method 14 sets flag bit 1 (the stream ends in a marker).  Whatever would need ZIP64
+    is refused."""
+    import struct
+    import time
+
+    n = len(names)
+    _check_writer_args(n, method, kind, strength, ae_version)
+    if not (len(payloads) == len(crcs) == len(usizes) == n):
+        raise _mz.MzHipError("names, payloads, crcs and usizes differ in length")
+    tm = time.localtime() if mtime is None else mtime
+    dos_time = (tm[3] << 11) | (tm[4] << 5) | (tm[5] >> 1)
+    dos_date = (max(tm[0] - 1980, 0) << 9) | (tm[1] << 5) | tm[2]
+    out, cd = bytearray(), bytearray()
+    for name, payload, crc, usize in zip(names, payloads, crcs, usizes):
+        raw = name.encode("utf-8") if isinstance(name, str) else bytes(name)
+        crc, usize = int(crc) & 0xFFFFFFFF, int(usize)
+        flag = (1 if kind else 0) | (2 if method == 14 else 0) | (0 if raw.isascii() else 0x800)
+        zmethod, extra, need = method, b"", 63 if method == 14 else 20
+        if kind == "aes":
+            extra = struct.pack("<HHH2sBH", MZ_ZIP_EXTENSION_AES, 7, ae_version, b"AE", strength, method)
+            zmethod, need = MZ_COMPRESS_METHOD_AES, 51
+            if ae_version == 2:
+                crc = 0
+        off = len(out)
+        if max(usize, len(payload), off) >= ZIP32_MAX or len(raw) > 0xFFFF:
+            raise _mz.MzHipError("entry %r needs ZIP64 (a size or offset of 4 GiB), which is not written" % (name,))
+        out += struct.pack("<IHHHHHIIIHH", 0x04034B50, need, flag, zmethod, dos_time, dos_date, crc, len(payload), usize,
+                           len(raw), len(extra))
+        out += raw + extra
+        out += payload
+        cd += struct.pack("<IHHHHHHIIIHHHHHII", 0x02014B50, need, need, flag, zmethod, dos_time, dos_date, crc,
+                          len(payload), usize, len(raw), len(extra), 0, 0, 0, 0, off)
+        cd += raw + extra
+    if max(len(out), len(cd)) >= ZIP32_MAX:
+        raise _mz.MzHipError("the archive needs ZIP64 (4 GiB), which is not written")
+    cd_off = len(out)
+    out += cd
+    out += struct.pack("<IHHHHIIH", 0x06054B50, 0, 0, n, n, len(cd), cd_off, 0)
+    return bytes(out)
+
+
+def encode_archive(entries, method=8, level=6, password=None, kind=None, strength=3, ae_version=2, entropy=os.urandom,
+                   device="cuda:0"):
+    """entries: (name, bytes-like) pairs -> the bytes of a ZIP archive, every entry compressed with `method` (0, 8 or 14) at
+    `level` and, with a password, encrypted as `kind` says ("pk" = ZipCrypto, "aes" = WinZip AES of `strength` 1..3, AE-1 or
+    AE-2).  One upload of the data, ONE codec launch (mzhip_deflate_batch_level, mzhip_lzma_encode_batch_preset in mode 0,
+    mzhip_crc32_batch for STORE) whose CRC words are the entries' CRCs, ZipCrypto's check bytes derived from those words on
+    the device, 10 n / 16 n bytes drawn from `entropy` (a callable: byte count -> bytes), ONE encrypt call
+    (mzhip_pkcrypt_encrypt_batch / mzhip_wzaes_encrypt_batch) straight from the codec's output, one copy back, and
+    assemble_archive on the host.  Not written: ZIP64 (65 535 entries or more, 4 GiB sizes or offsets: MzHipError), data
+    descriptors, method 95."""
+    import torch
+
+    entries = [(name, np.frombuffer(bytes(data), dtype=np.uint8)) for name, data in entries]
+    n = len(entries)
+    _check_writer_args(n, method, kind, strength, ae_version)
+    if (kind is None) != (password is None):
+        raise _mz.MzHipError("a kind needs a password and a password needs a kind")
+    usize = np.array([d.size for _, d in entries], dtype=np.int64)
+    over = crypt_overhead(kind, strength)
+    slack = 0 if method == 0 else 64 if method == 8 else 1024          # include/mzhip.h: what always suffices
+    cap = usize if method == 0 else usize + usize // 8 + slack
+    if n and int((cap + over).max()) >= ZIP32_MAX:
+        raise _mz.MzHipError("an entry of 4 GiB needs ZIP64, which is not written")
+    names = [name for name, _ in entries]
+    if n == 0:
+        return assemble_archive([], [], [], [], method, kind, strength, ae_version)
+    _mz.require_gpu()
+    dev = torch.device(device)
+    L = _mz.lib()
+
+    def offsets(sizes):   # 16-byte aligned slots -> (offsets, total)
+        slot = (sizes + 15) // 16 * 16
+        off = np.zeros(n, dtype=np.int64)
+        np.cumsum(slot[:-1], out=off[1:])
+        return off, int(off[-1] + slot[-1])
+
+    def dev_u32(a):
+        return torch.from_numpy(np.ascontiguousarray(a).astype(np.uint32).view(np.int32)).to(dev)
+
+    in_off, in_total = offsets(usize)
+    blob = np.zeros(max(in_total, 16), dtype=np.uint8)
+    for o, (_, d) in zip(in_off, entries):
+        blob[o:o + d.size] = d
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        d_in = torch.from_numpy(blob).to(dev)
+        d_in_off, d_in_len = torch.from_numpy(in_off).to(dev), dev_u32(usize)
+        r_len, r_crc, r_st = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(3))
+        if method == 0:
+            rc = L.mzhip_crc32_batch(d_in.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), n, None, r_crc.data_ptr(), stream)
+            d_comp, d_comp_off, r_len = d_in, d_in_off, d_in_len
+        else:
+            comp_off, comp_total = offsets(cap)
+            d_comp = torch.empty(max(comp_total, 16), dtype=torch.uint8, device=dev)
+            d_comp_off, d_cap = torch.from_numpy(comp_off).to(dev), dev_u32(cap)
+            if method == 8:
+                rc = L.mzhip_deflate_batch_level(d_in.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), d_comp.data_ptr(),
+                                                 d_comp_off.data_ptr(), d_cap.data_ptr(), None, n, level, 15, r_len.data_ptr(),
+                                                 r_crc.data_ptr(), r_st.data_ptr(), stream)
+            else:
+                rc = L.mzhip_lzma_encode_batch_preset(d_in.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), int(usize.max()),
+                                                      d_comp.data_ptr(), d_comp_off.data_ptr(), d_cap.data_ptr(), None, n, level,
+                                                      r_len.data_ptr(), r_crc.data_ptr(), r_st.data_ptr(), stream)
+        if rc != 0:
+            raise _mz.MzHipError("codec launch failed: %d %s" % (rc, L.mzhip_last_error().decode()))
+        e_len, e_st = r_len, torch.zeros(n, dtype=torch.int32, device=dev)
+        d_pay, pay_off = d_comp, None
+        if kind is not None:
+            pw = bytes(password)
+            pay_off, pay_total = offsets(cap + over)
+            d_pay = torch.empty(max(pay_total, 16), dtype=torch.uint8, device=dev)
+            d_pay_off = torch.from_numpy(pay_off).to(dev)
+            e_len = torch.zeros(n, dtype=torch.int32, device=dev)
+            rnd = bytes(entropy((10 if kind == "pk" else 16) * n))
+            if len(rnd) != (10 if kind == "pk" else 16) * n:
+                raise _mz.MzHipError("entropy() returned %d bytes" % len(rnd))
+            d_rnd = torch.from_numpy(np.frombuffer(rnd, dtype=np.uint8).copy()).to(dev)
+            if kind == "pk":
+                # plain header byte 11 = the CRC's top byte, byte 10 the next one (mz_zip_get_pk_verify, flag bit 3 clear)
+                d_ver = (((r_crc >> 24) & 255) | (((r_crc >> 16) & 255) << 8)).to(torch.int32)
+                rc = L.mzhip_pkcrypt_encrypt_batch(d_comp.data_ptr(), d_comp_off.data_ptr(), r_len.data_ptr(), d_pay.data_ptr(),
+                                                   d_pay_off.data_ptr(), n, pw, len(pw), d_ver.data_ptr(), d_rnd.data_ptr(),
+                                                   e_len.data_ptr(), e_st.data_ptr(), stream)
+            else:
+                d_str = torch.full((n,), strength, dtype=torch.uint8, device=dev)
+                rc = L.mzhip_wzaes_encrypt_batch(d_comp.data_ptr(), d_comp_off.data_ptr(), r_len.data_ptr(), d_str.data_ptr(),
+                                                 d_rnd.data_ptr(), d_pay.data_ptr(), d_pay_off.data_ptr(), n, pw, len(pw),
+                                                 e_len.data_ptr(), e_st.data_ptr(), stream)
+            if rc != 0:
+                raise _mz.MzHipError("encrypt launch failed: %d %s" % (rc, L.mzhip_last_error().decode()))
+        res = torch.stack((r_crc, r_st, e_len, e_st)).cpu().numpy()   # (synchronises with the stream)
+        crc, c_st, p_len, p_st = res[0].view(np.uint32), res[1], res[2].view(np.uint32).astype(np.int64), res[3]
+        if (c_st != 0).any() or (p_st != 0).any():
+            i = int(np.flatnonzero((c_st != 0) | (p_st != 0))[0])
+            raise _mz.MzHipError("entry %d (%r): codec status %d, crypt status %d" % (i, names[i], c_st[i], p_st[i]))
+        if method == 0 and kind is None:
+            payloads = [d.tobytes() for _, d in entries]   # the payload IS the data: nothing to copy back
+        else:
+            h_pay = d_pay.cpu().numpy()
+            if pay_off is None:
+                pay_off = comp_off
+            payloads = [h_pay[int(o):int(o) + int(k)].tobytes() for o, k in zip(pay_off, p_len)]
+    return assemble_archive(names, payloads, crc, usize, method, kind, strength, ae_version)

@@ -1,5 +1,5 @@
 /* crypt_core.h -- the two crypt streams the reference puts between the archive and the codec of a password-protected
- * entry (mz_zip.c, the use_crypt branch of the entry-stack build), read side only:
+ * entry (mz_zip.c, the use_crypt branch of the entry-stack build), both directions (the write side is at the end):
  *   - PKWARE traditional encryption ("ZipCrypto", APPNOTE 6.1): three 32-bit keys updated per byte -- a strictly serial
  *     recurrence, so the parallel axis is entries: one LANE per entry, like k_sha_batch;
  *   - WinZip AES (AE-1 / AE-2): PBKDF2-HMAC-SHA1 (RFC 8018 5.2, RFC 2104) key derivation -- serial chains of 2 x 1000
@@ -376,6 +376,106 @@ MZ_DEV int32_t mz_wzaes_auth(const uint8_t *in, uint32_t in_len, uint32_t streng
         diff |= m ^ a[i];
     }
     return diff ? MZ_CRYPT_CRC_ERROR : MZ_CRYPT_OK;
+}
+
+/* ---- the write side -------------------------------------------------------------------------------------------- */
+/* Both formats are fully determined by the plaintext, the password and the random bytes the CALLER supplies (the 10 free
+ * bytes of the ZipCrypto header, the AES salt): there is no entropy source down here. */
+
+MZ_DEV uint32_t mz_pk_encode(uint32_t &k0, uint32_t &k1, uint32_t &k2, uint32_t p, const uint32_t *tab) {
+    const uint32_t c = (p ^ mz_pk_stream_byte(k2)) & 255u;
+    mz_pk_update(k0, k1, k2, p, tab); /* the keys follow the PLAIN byte in both directions */
+    return c;
+}
+
+/* One entry, by ONE lane: out[0 .. in_len + 12) = the encrypted 12-byte header + the encrypted payload.  header10 = the ten
+ * free header bytes; verify as on the read side: bits 8-15 become plain header byte 10, bits 0-7 byte 11 (bit 16 means
+ * nothing here).  The payload goes 16 bytes at a time from the first 16-byte boundary of the INPUT on, as mz_pkcrypt_entry
+ * reads it.  An in_len whose out_len does not fit 32 bits: MZ_CRYPT_PARAM_ERROR, nothing written. */
+MZ_DEV int32_t mz_pkcrypt_encrypt_entry(const uint8_t *in, uint32_t in_len, uint8_t *out, const uint8_t *header10, uint32_t verify,
+                                        uint32_t k0, uint32_t k1, uint32_t k2, const uint32_t *tab, uint32_t *out_len) {
+    *out_len = 0;
+    if (in_len > 0xFFFFFFFFu - MZ_PK_HEADER) return MZ_CRYPT_PARAM_ERROR;
+    for (uint32_t i = 0; i < 10u; i++) out[i] = (uint8_t)mz_pk_encode(k0, k1, k2, header10[i], tab);
+    out[10] = (uint8_t)mz_pk_encode(k0, k1, k2, (verify >> 8) & 255u, tab);
+    out[11] = (uint8_t)mz_pk_encode(k0, k1, k2, verify & 255u, tab);
+    uint8_t *o = out + MZ_PK_HEADER;
+    const uint32_t n = in_len;
+    uint32_t i = 0;
+    uint32_t head = (uint32_t)(0u - (uint32_t)(uintptr_t)in) & 15u;
+    if (head > n) head = n;
+    for (; i < head; i++) o[i] = (uint8_t)mz_pk_encode(k0, k1, k2, in[i], tab);
+    for (; i + 16u <= n; i += 16u) {
+        uint32_t q[4];
+        __builtin_memcpy(q, in + i, 16);
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            uint32_t r = 0;
+#pragma unroll
+            for (int b = 0; b < 4; b++) r |= mz_pk_encode(k0, k1, k2, (q[w] >> (8 * b)) & 255u, tab) << (8 * b);
+            q[w] = r;
+        }
+        __builtin_memcpy(o + i, q, 16);
+    }
+    for (; i < n; i++) o[i] = (uint8_t)mz_pk_encode(k0, k1, k2, in[i], tab);
+    *out_len = n + MZ_PK_HEADER;
+    return MZ_CRYPT_OK;
+}
+
+/* WinZip AES: out = salt(4s + 4) | verifier(2) | ciphertext(in_len) | authcode(10).  The entry's verdict before any key
+ * material: MZ_CRYPT_OK, or PARAM for a strength outside 1..3 and for an in_len whose out_len does not fit 32 bits. */
+MZ_DEV int32_t mz_wzaes_enc_precheck(uint32_t in_len, uint32_t strength) {
+    if (strength < 1u || strength > 3u) return MZ_CRYPT_PARAM_ERROR;
+    if (in_len > 0xFFFFFFFFu - (mz_wzaes_salt_len(strength) + MZ_WZAES_VERIFY + MZ_WZAES_AUTH)) return MZ_CRYPT_PARAM_ERROR;
+    return MZ_CRYPT_OK;
+}
+
+/* Key step 1, one lane per (entry, block 0..3), as mz_wzaes_km_block with the salt from the caller's record */
+MZ_DEV void mz_wzaes_enc_km_block(const mz_hmac_sha1_key *pw, const uint8_t *salt, uint32_t in_len, uint32_t strength, uint32_t b,
+                                  mz_wzaes_entry_keys *ek) {
+    if (mz_wzaes_enc_precheck(in_len, strength) != MZ_CRYPT_OK || b >= mz_wzaes_km_blocks(strength)) return;
+    uint32_t t[5];
+    mz_pbkdf2_sha1_block(pw, salt, mz_wzaes_salt_len(strength), MZ_WZAES_ITER, b + 1u, t);
+#pragma unroll
+    for (int i = 0; i < 5; i++) mz_st4(ek->km + 20u * b + 4u * (uint32_t)i, __builtin_bswap32(t[i]));
+}
+
+/* Key step 2, one lane per entry, behind step 1 of all its blocks: nothing to compare -- the lane WRITES salt and verifier
+ * to the front of the output and leaves round keys, HMAC pad states and the status in the record -> status */
+MZ_DEV int32_t mz_wzaes_enc_finish_keys(const uint8_t *salt, uint32_t in_len, uint32_t strength, uint8_t *out,
+                                        mz_wzaes_entry_keys *ek, uint32_t *out_len) {
+    *out_len = 0;
+    const int32_t st = mz_wzaes_enc_precheck(in_len, strength);
+    if (st == MZ_CRYPT_OK) {
+        const uint32_t sl = mz_wzaes_salt_len(strength), kl = mz_wzaes_key_len(strength);
+        for (uint32_t i = 0; i < sl; i++) out[i] = salt[i];
+        out[sl] = ek->km[2u * kl];
+        out[sl + 1u] = ek->km[2u * kl + 1u];
+        ek->rounds = mz_aes_expand_key(ek->km, kl, ek->rk); /* straight into the scratch: no indexed private array */
+        mz_hmac_sha1_key mk;
+        mz_hmac_sha1_init(&mk, ek->km + kl, kl);
+        ek->mac = mk;
+        *out_len = in_len + sl + MZ_WZAES_VERIFY + MZ_WZAES_AUTH;
+    }
+    ek->status = st;
+    return st;
+}
+
+/* (the CTR step is mz_wzaes_ctr itself, plaintext in, out + salt_len + 2: CTR is its own inverse) */
+
+/* Authentication step, one lane per entry, BEHIND the CTR step: HMAC-SHA1 over the ciphertext that step wrote into out,
+ * first 10 bytes stored behind it */
+MZ_DEV void mz_wzaes_enc_auth(uint8_t *out, uint32_t in_len, uint32_t strength, const mz_wzaes_entry_keys *ek) {
+    const uint32_t sl = mz_wzaes_salt_len(strength);
+    uint8_t *ct = out + sl + MZ_WZAES_VERIFY;
+    mz_hmac_sha1_key mk = ek->mac;
+    uint32_t mac[5];
+    mz_hmac_sha1(&mk, ct, in_len, mac);
+    uint8_t *a = ct + in_len;
+    for (uint32_t i = 0; i < MZ_WZAES_AUTH; i++) {
+        const uint32_t w = i >> 2;
+        a[i] = (uint8_t)((w == 0 ? mac[0] : w == 1 ? mac[1] : mac[2]) >> (24u - 8u * (i & 3u)));
+    }
 }
 
 #endif

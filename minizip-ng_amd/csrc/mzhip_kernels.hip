@@ -499,6 +499,107 @@ __global__ __launch_bounds__(256, 4) void k_wzaes_auth(WzaesArgs a) {
     if (st != 0) a.status[e] = st;
 }
 
+// K8, write side: the same streams in the encrypting direction.  The random bytes (ZipCrypto header, AES salt) are the caller's.
+struct PkcryptEncArgs {
+    const uint8_t *in;
+    const uint64_t *in_off;
+    const uint32_t *in_len;
+    uint8_t *out;
+    const uint64_t *out_off;
+    uint32_t n;
+    uint32_t k0, k1, k2;    // the three keys after the password (host: mz_pk_init_keys_host)
+    const uint32_t *verify; // per entry: bits 8-15 -> plain header byte 10, bits 0-7 -> byte 11
+    const uint8_t *header;  // per entry: the 10 free header bytes
+    uint32_t *out_len;
+    int32_t *status;
+    const mzhip_crc_tables *tabs;
+};
+
+// ZipCrypto: ONE LANE encrypts one entry, as k_pkcrypt_batch decrypts it.
+__global__ __launch_bounds__(256) void k_pkcrypt_enc_batch(PkcryptEncArgs a) {
+    __shared__ uint32_t crc_tab[256];
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) crc_tab[i] = a.tabs->byte_tab[i];
+    __syncthreads();
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.n) return;
+    uint32_t out_len;
+    a.status[e] = mz_pkcrypt_encrypt_entry(a.in + a.in_off[e], a.in_len[e], a.out + a.out_off[e], a.header + (size_t)e * 10u, a.verify[e],
+                                           a.k0, a.k1, a.k2, crc_tab, &out_len);
+    a.out_len[e] = out_len;
+}
+
+struct WzaesEncArgs {
+    const uint8_t *in;
+    const uint64_t *in_off;
+    const uint32_t *in_len;
+    const uint8_t *strength;
+    const uint8_t *salt; // per entry a 16-byte record, 4 s + 4 bytes of it used
+    uint8_t *out;
+    const uint64_t *out_off;
+    uint32_t n;
+    uint32_t password_len;
+    uint8_t password[MZ_WZAES_PW_MAX];
+    uint32_t *out_len;
+    int32_t *status;
+    uint32_t *counter;
+    mz_wzaes_entry_keys *keys; // n records of scratch
+};
+
+// Key derivation as k_wzaes_keys: four lane slots per entry, a workgroup barrier, then the slot-0 lane -- which here has
+// nothing to compare: it writes salt and verifier to the front of the entry's output.  No lane leaves before the barrier.
+__global__ __launch_bounds__(256) void k_wzaes_enc_keys(WzaesEncArgs a) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, e = t >> 2, b = t & 3u;
+    const bool live = e < a.n;
+    const uint8_t *salt = nullptr;
+    uint32_t in_len = 0, strength = 0;
+    if (live) {
+        salt = a.salt + (size_t)e * 16u;
+        in_len = a.in_len[e];
+        strength = a.strength[e];
+        mz_hmac_sha1_key pw;
+        mz_hmac_sha1_init(&pw, a.password, a.password_len);
+        mz_wzaes_enc_km_block(&pw, salt, in_len, strength, b, a.keys + e);
+    }
+    __syncthreads(); // the km bytes of the entry's other slots (global memory, workgroup scope)
+    if (live && b == 0) {
+        uint32_t out_len;
+        a.status[e] = mz_wzaes_enc_finish_keys(salt, in_len, strength, a.out + a.out_off[e], a.keys + e, &out_len);
+        a.out_len[e] = out_len;
+    }
+}
+
+// AES-CTR as k_wzaes_ctr, plaintext in: one wave per entry on the persistent grid, the ciphertext goes behind the salt and the
+// verifier (4 s + 6 bytes off the input's alignment).  Entries whose key step refused them are skipped.
+__global__ __launch_bounds__(MZ_WAVES_PER_WG * 64) void k_wzaes_enc_ctr(WzaesEncArgs a) {
+    __shared__ mz_aes_tables tab;
+    for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) mz_aes_table_entry(&tab, i);
+    __syncthreads();
+    MZ_LANE_DECL
+    for (;;) {
+        uint32_t e;
+        MZ_WAVE_FETCH_ADD(e, a.counter);
+        if (e >= a.n) break;
+        const mz_wzaes_entry_keys *ek = a.keys + e;
+        if (MZ_UNIFORM((uint32_t)ek->status) != 0u) continue;
+        const uint32_t strength = MZ_UNIFORM((uint32_t)a.strength[e]), sl = mz_wzaes_salt_len(strength);
+        const uint32_t n = MZ_UNIFORM(a.in_len[e]);
+        const uint64_t io = a.in_off[e], oo = a.out_off[e];
+        const uint8_t *in = a.in + (((uint64_t)MZ_UNIFORM((uint32_t)(io >> 32)) << 32) | MZ_UNIFORM((uint32_t)io));
+        uint8_t *out = a.out + (((uint64_t)MZ_UNIFORM((uint32_t)(oo >> 32)) << 32) | MZ_UNIFORM((uint32_t)oo));
+        mz_wzaes_ctr(in, n, out + sl + MZ_WZAES_VERIFY, ek->rk, MZ_UNIFORM(ek->rounds), &tab);
+    }
+}
+
+// Authentication: one lane per entry.  Unlike k_wzaes_auth it reads what the CTR kernel WROTE, so it must be queued behind
+// that kernel on the same stream; it is the only writer of the entry's last 10 bytes.
+__global__ __launch_bounds__(256, 4) void k_wzaes_enc_auth(WzaesEncArgs a) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.n) return;
+    const mz_wzaes_entry_keys *ek = a.keys + e;
+    if (ek->status != 0) return;
+    mz_wzaes_enc_auth(a.out + a.out_off[e], a.in_len[e], a.strength[e], ek);
+}
+
 struct DeflateArgs {
     const uint8_t *in;
     const uint64_t *in_off;

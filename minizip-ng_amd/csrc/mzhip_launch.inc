@@ -555,6 +555,88 @@ int32_t mzhip_wzaes_batch(const void *d_in, const uint64_t *d_in_off, const uint
     return rc;
 }
 
+int32_t mzhip_pkcrypt_encrypt_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
+                                    const uint64_t *d_out_off, uint32_t n, const uint8_t *password, uint32_t password_len,
+                                    const uint32_t *d_verify, const uint8_t *d_header, uint32_t *d_out_len, int32_t *d_status,
+                                    void *stream) {
+    if (!password) return MZ_CRYPT_PARAM_ERROR;
+    if (n == 0) return 0;
+    DeviceCtx *c = nullptr;
+    int32_t rc = ctx_for_current(&c);
+    if (rc) return rc;
+    PkcryptEncArgs a;
+    a.in = (const uint8_t *)d_in;
+    a.in_off = d_in_off;
+    a.in_len = d_in_len;
+    a.out = (uint8_t *)d_out;
+    a.out_off = d_out_off;
+    a.n = n;
+    uint32_t keys[3];
+    mz_pk_init_keys_host(password, password_len, keys);
+    a.k0 = keys[0];
+    a.k1 = keys[1];
+    a.k2 = keys[2];
+    a.verify = d_verify;
+    a.header = d_header;
+    a.out_len = d_out_len;
+    a.status = d_status;
+    a.tabs = c->d_tabs;
+    hipLaunchKernelGGL(k_pkcrypt_enc_batch, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int32_t mzhip_wzaes_encrypt_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, const uint8_t *d_strength,
+                                  const uint8_t *d_salt, void *d_out, const uint64_t *d_out_off, uint32_t n, const uint8_t *password,
+                                  uint32_t password_len, uint32_t *d_out_len, int32_t *d_status, void *stream) {
+    if (!password || password_len > MZ_WZAES_PW_MAX) return MZ_CRYPT_PARAM_ERROR;
+    if (n == 0) return 0;
+    if (n > 0x3FFFFFFFu) return MZ_CRYPT_PARAM_ERROR; /* four lane slots per entry in a 32-bit thread index */
+    DeviceCtx *c = nullptr;
+    int32_t rc = ctx_for_current(&c);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    WzaesEncArgs a;
+    a.in = (const uint8_t *)d_in;
+    a.in_off = d_in_off;
+    a.in_len = d_in_len;
+    a.strength = d_strength;
+    a.salt = d_salt;
+    a.out = (uint8_t *)d_out;
+    a.out_off = d_out_off;
+    a.n = n;
+    a.password_len = password_len;
+    memset(a.password, 0, sizeof(a.password));
+    memcpy(a.password, password, password_len);
+    a.out_len = d_out_len;
+    a.status = d_status;
+    CounterLease lease;
+    rc = lease.get(c, s);
+    if (rc) return rc;
+    a.counter = lease.p;
+    int slot = -1;
+    void *scratch = nullptr;
+    rc = scratch_acquire(c, (size_t)n * sizeof(mz_wzaes_entry_keys), s, &slot, &scratch);
+    if (rc) return rc;
+    a.keys = (mz_wzaes_entry_keys *)scratch;
+    const char *what = "k_wzaes_enc_keys";
+    hipLaunchKernelGGL(k_wzaes_enc_keys, dim3((uint32_t)(((uint64_t)n * 4u + 255u) / 256u)), dim3(256), 0, s, a);
+    hipError_t le = hipGetLastError();
+    if (le == hipSuccess) {
+        what = "k_wzaes_enc_ctr";
+        hipLaunchKernelGGL(k_wzaes_enc_ctr, dim3(grid_for(c, n)), dim3(MZ_WAVES_PER_WG * 64), 0, s, a);
+        le = hipGetLastError();
+    }
+    if (le == hipSuccess) { /* behind the CTR kernel: it authenticates the ciphertext that kernel wrote */
+        what = "k_wzaes_enc_auth";
+        hipLaunchKernelGGL(k_wzaes_enc_auth, dim3((n + 255) / 256), dim3(256), 0, s, a);
+        le = hipGetLastError();
+    }
+    rc = scratch_release(c, slot, s);
+    if (le != hipSuccess) return fail(what, le);
+    return rc;
+}
+
 int32_t mzhip_deflate_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
                             const uint64_t *d_out_off, const uint32_t *d_out_cap, const uint8_t *d_final, uint32_t n,
                             uint32_t *d_out_len, uint32_t *d_crc, int32_t *d_status, void *stream) {
