@@ -217,6 +217,29 @@ MZHIP_API int32_t mzhip_xz_batch(const void *d_in, const uint64_t *d_in_off, con
                                  uint32_t n, uint32_t *d_out_len, uint32_t *d_in_used, uint32_t *d_crc,
                                  int32_t *d_status, void *stream);
 
+/* bzip2 decode (ZIP method 12) with fused CRC-32 ---------------------------------------- */
+
+/* Replaces, for n method-12 entries at once, mz_stream_bzip_read (mz_strm_bzip.c -> libbz2 BZ2_bzDecompress) +
+ * mz_crypt_crc32_update (mz_zip.c:2049).  Signature and memory contract of mzhip_inflate_batch, with one difference: the
+ * input is read at BYTE granularity, never outside d_in + d_in_off[i] .. + d_in_len[i].  Entry i's input is ONE bzip2
+ * stream ("BZh1" .. "BZh9", blocks, end marker, combined CRC) as BZ2_bzDecompress reads it: bytes behind the stream are
+ * not consumed, d_in_used = whole bytes through the one that holds the last bit of the combined CRC.  One wave per
+ * entry; every block's CRC and the combined CRC are verified on the device.
+ * Status: 0 the stream ended and both CRC levels matched; -3 whatever libbz2 calls a data or magic error; -5 the input
+ * ended before the stream did (d_in_len 0 included); -200 a block's bytes do not fit d_out_cap; -109 a block with the
+ * "randomised" bit set (no compressor has written one since bzip2 0.9.5; the one deviation from libbz2, which decodes
+ * them).  The first problem in stream order decides.  With a status other than 0, d_out_len counts the bytes of the
+ * blocks in front of the problem that checked out and d_crc is the CRC-32 of those. */
+MZHIP_API int32_t mzhip_bzip2_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
+                                    const uint64_t *d_out_off, const uint32_t *d_out_cap, uint32_t n, uint32_t *d_out_len,
+                                    uint32_t *d_in_used, uint32_t *d_crc, int32_t *d_status, void *stream);
+/* one stream from a host buffer (H2D + kernel + D2H, synchronous), like mzhip_lzma_host; returns the status */
+MZHIP_API int32_t mzhip_bzip2_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, uint32_t *out_len,
+                                   uint32_t *in_used, uint32_t *crc);
+/* What a mzhip_bzip2_batch launch of n entries would use: single-wave workgroups (min(n, resident waves of the device))
+ * and bytes of device scratch (the inverse-BWT arrays, per wave of the grid). */
+MZHIP_API void mzhip_bzip2_launch_geometry(uint32_t n, uint32_t *grid, uint64_t *scratch_bytes);
+
 /* SHA-1 / SHA-224 / SHA-256 / SHA-384 / SHA-512 of n buffers ----------------------------- */
 
 /* What the reader's hash verification computes per entry on the CPU: mz_crypt_sha_begin/_update/_end over the

@@ -411,6 +411,43 @@ int32_t mzhip_xz_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t
     return lzma_family_host(1, in, in_len, out, out_cap, max_out, out_len, in_used, crc);
 }
 
+// One bzip2 stream (ZIP method 12) from a host buffer.
+int32_t mzhip_bzip2_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, uint32_t *out_len, uint32_t *in_used,
+                         uint32_t *crc) {
+    DeviceCtx *c = nullptr;
+    int32_t rc = ctx_for_current(&c);
+    if (rc) return rc;
+    const size_t in_pad = ((size_t)in_len + 15) & ~(size_t)15;
+    const size_t total = 64 + in_pad + out_cap + 16;
+    Staging sc;
+    rc = sc.get(c, total);
+    if (rc) return rc;
+    uint8_t *base = (uint8_t *)sc.p;
+    struct Meta {
+        uint64_t in_off, out_off;
+        uint32_t in_len, out_cap, out_len, in_used, crc;
+        int32_t status;
+    } m;
+    memset(&m, 0, sizeof(m));
+    m.in_off = 64;
+    m.out_off = 64 + in_pad;
+    m.in_len = in_len;
+    m.out_cap = out_cap;
+    HIP_TRY(mz_h2d(base, &m, sizeof(m)));
+    if (in_len) HIP_TRY(mz_h2d(base + 64, in, in_len));
+    Meta *dm = (Meta *)base;
+    rc = mzhip_bzip2_batch(base, &dm->in_off, &dm->in_len, base, &dm->out_off, &dm->out_cap, 1, &dm->out_len, &dm->in_used, &dm->crc,
+                           &dm->status, MZ_HOST_STREAM);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
+    HIP_TRY(mz_d2h(&m, base, sizeof(m)));
+    if (m.out_len && out) HIP_TRY(mz_d2h(out, base + m.out_off, m.out_len));
+    if (out_len) *out_len = m.out_len;
+    if (in_used) *in_used = m.in_used;
+    if (crc) *crc = m.crc;
+    return m.status;
+}
+
 // One ZIP method-14 payload from a host buffer.
 int32_t mzhip_lzma_encode_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, uint32_t *out_len,
                                uint32_t *crc) {

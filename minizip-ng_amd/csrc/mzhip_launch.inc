@@ -448,6 +448,65 @@ int32_t mzhip_xz_batch(const void *d_in, const uint64_t *d_in_off, const uint32_
                              d_crc, d_status, stream);
 }
 
+/* bzip2: the inverse BWT of a block needs MZ_BZ_SCRATCH_BYTES = 4 518 144 bytes of HBM per resident wave (4 bytes of link
+ * and first-column byte per symbol of a 900 000-symbol block, the block's 900 000 bytes, 18 002 selectors).  8 single-wave
+ * workgroups per CU, two per SIMD: the chain walk is one dependent load per byte, so a wave mostly waits and more waves
+ * would hide more of it -- LDS (10.4 KiB per wave) would allow 15 -- but every further wave per CU costs 1.1 GiB of
+ * scratch on a 256-CU device; 8 per CU is 8.6 GiB for a full grid.  grid = min(n, resident): a small batch costs a small
+ * scratch. */
+#define MZ_BZ_WAVES_PER_CU 8u
+
+static uint32_t bzip2_grid(const DeviceCtx *c, uint32_t n) {
+    const uint32_t resident = (uint32_t)c->cu_count * MZ_BZ_WAVES_PER_CU;
+    return n < resident ? n : resident;
+}
+
+void mzhip_bzip2_launch_geometry(uint32_t n, uint32_t *grid, uint64_t *scratch_bytes) {
+    DeviceCtx *c = nullptr;
+    uint32_t g = 0;
+    if (ctx_for_current(&c) == 0) g = bzip2_grid(c, n);
+    if (grid) *grid = g;
+    if (scratch_bytes) *scratch_bytes = (uint64_t)g * MZ_BZ_SCRATCH_BYTES;
+}
+
+int32_t mzhip_bzip2_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
+                          const uint64_t *d_out_off, const uint32_t *d_out_cap, uint32_t n, uint32_t *d_out_len,
+                          uint32_t *d_in_used, uint32_t *d_crc, int32_t *d_status, void *stream) {
+    if (n == 0) return 0;
+    DeviceCtx *c = nullptr;
+    int32_t rc = ctx_for_current(&c);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Bzip2Args a;
+    a.in = (const uint8_t *)d_in;
+    a.in_off = d_in_off;
+    a.in_len = d_in_len;
+    a.out = (uint8_t *)d_out;
+    a.out_off = d_out_off;
+    a.out_cap = d_out_cap;
+    a.n = n;
+    a.out_len = d_out_len;
+    a.in_used = d_in_used;
+    a.crc = d_crc;
+    a.status = d_status;
+    CounterLease lease;
+    rc = lease.get(c, s);
+    if (rc) return rc;
+    a.counter = lease.p;
+    a.tabs = c->d_tabs;
+    const uint32_t grid = bzip2_grid(c, n);
+    int slot = -1;
+    void *scratch = nullptr;
+    rc = scratch_acquire(c, (size_t)grid * MZ_BZ_SCRATCH_BYTES, s, &slot, &scratch);
+    if (rc) return rc;
+    a.scratch = (uint8_t *)scratch;
+    hipLaunchKernelGGL(k_bzip2_batch, dim3(grid), dim3(64), 0, s, a);
+    const hipError_t le = hipGetLastError();
+    rc = scratch_release(c, slot, s);
+    if (le != hipSuccess) return fail("k_bzip2_batch", le);
+    return rc;
+}
+
 int32_t mzhip_sha_batch(const void *d_buf, const uint64_t *d_off, const uint32_t *d_len, uint32_t n, uint32_t algorithm,
                         void *d_digest, void *stream) {
     if (algorithm != 20 && (algorithm < 22 || algorithm > 25)) return MZHIP_STATUS_UNSUPPORTED;
