@@ -572,11 +572,10 @@ int32_t mzhip_gather_results(void *comm, int32_t rank, int32_t world, const int6
     DeviceCtx *c = nullptr;
     int32_t rc = ctx_for_current(&c);
     if (rc) return rc;
-    int slot = -1;
-    void *p = nullptr;
-    rc = scratch_acquire(c, (size_t)(world + 1) * 2 * (size_t)mx * 4, s, &slot, &p);
+    ScratchLease sc;
+    rc = sc.get(ctx_scratch(c), (size_t)(world + 1) * 2 * (size_t)mx * 4, s);
     if (rc) return rc;
-    uint32_t *send = (uint32_t *)p, *recv = send + 2 * mx;
+    uint32_t *send = (uint32_t *)sc.p, *recv = send + 2 * mx;
     hipError_t e = hipSuccess;
     if (n_local) {
         e = hipMemcpyAsync(send, d_crc, (size_t)n_local * 4, hipMemcpyDeviceToDevice, s);
@@ -590,7 +589,6 @@ int32_t mzhip_gather_results(void *comm, int32_t rank, int32_t world, const int6
         e = hipMemcpyAsync(d_crc_all + bounds[r], recv + (size_t)r * 2 * mx, (size_t)cnt * 4, hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d_status_all + bounds[r], recv + (size_t)r * 2 * mx + mx, (size_t)cnt * 4, hipMemcpyDeviceToDevice, s);
     }
-    (void)scratch_release(c, slot, s);
     if (e != hipSuccess) return fail("mzhip_gather_results", e);
     if (nr != 0) {
         snprintf(g_err, sizeof(g_err), "mzhip_gather_results: ncclAllGather returned %d", nr);

@@ -1,10 +1,14 @@
 // mzhip_launch.inc -- the launch side of libmzhip.so's runtime, textually included by mzhip_kernels.hip: everything whose body
-// names a kernel, a kernel argument struct or a constant of a *_core.h.  Device context, scratch and work-queue caches, the
-// launchers of the batch C ABI (include/mzhip.h), and the host-buffer entry points that launch kernels themselves (the many-wave
-// inflate, the resumable LZMA coders, the .xz writer, the DEFLATE segment writer).  It holds no device code.  The rest of the
-// runtime -- stream pool, staging, CRC lane, gather, prime caches -- is built apart from the kernels (mzhip_host.cpp,
-// mzhip_crc_host.cpp, mzhip_prime.cpp); mzhip_runtime.h declares what crosses.
+// names a kernel, a kernel argument struct or a constant of a *_core.h.  Device context, the launchers of the batch C ABI
+// (include/mzhip.h), and the host-buffer entry points that launch kernels themselves (the many-wave inflate, the resumable
+// LZMA coders, the .xz writer, the DEFLATE segment writer); the scratch and work-queue caches every launch leases from are
+// mzhip_slots.inc, defined here.  It holds no device code.  The rest of the runtime -- stream pool, staging, CRC lane, gather,
+// prime caches -- is built apart from the kernels (mzhip_host.cpp, mzhip_crc_host.cpp, mzhip_prime.cpp); mzhip_runtime.h
+// declares what crosses.
 // ---------------------------------------------------------------------------------- host
+
+#define MZHIP_SLOTS_DEFINE
+#include "mzhip_slots.inc"
 
 using namespace mzh;
 
@@ -14,20 +18,8 @@ struct DeviceCtx {
     bool ready = false;
     mzhip_crc_tables *d_tabs = nullptr;
     uint64_t *d_tab64 = nullptr;
-    struct ScratchEnt {
-        void *p = nullptr;
-        size_t cap = 0;
-        hipEvent_t ev = nullptr;    // recorded behind the last launch that used the buffer
-        hipStream_t last = nullptr; // ... on this stream
-        bool used = false, held = false;
-    } scratch[32]; // per-launch scratch (K4 / K6 tokens) and the host-buffer calls' staging, see scratch_acquire()
-    uint32_t *d_counters = nullptr; // MZ_NUM_COUNTERS work-queue heads, see CounterLease
-    struct CounterSlot {
-        hipEvent_t ev = nullptr;    // recorded behind the last launch that used the counter
-        hipStream_t last = nullptr; // ... on this stream
-        bool used = false, held = false;
-    } cslots[MZ_NUM_COUNTERS];
-    uint32_t next_counter = 0;
+    ScratchCache scratch;  // per-launch scratch (K1 records, K4 / K6 tokens, ...) and the host-buffer calls' staging
+    CounterCache counters; // the work-queue heads of the launches
     int cu_count = 0;
     int inflate_wgs_per_cu = 1;
     // the four-candidate classes of K4 / the LZ tokenizer need > 64 KiB of dynamic LDS per workgroup: asked for once per
@@ -51,11 +43,11 @@ bool big_lds_ok(std::atomic<int> &state, const void *kernel, size_t bytes) {
 }
 
 DeviceCtx g_ctx[kMaxDevices];
-std::mutex g_mu;
 
 } // namespace
 
 int mzh::ctx_device(const DeviceCtx *c) { return (int)(c - g_ctx); }
+ScratchCache *mzh::ctx_scratch(DeviceCtx *c) { return &c->scratch; }
 
 int32_t mzh::ctx_for_current(DeviceCtx **out) {
     int dev = 0;
@@ -75,7 +67,7 @@ int32_t mzh::ctx_for_current(DeviceCtx **out) {
         mzhip_crc64_table_init(t64);
         HIP_TRY(hipMalloc((void **)&c.d_tab64, sizeof(t64)));
         HIP_TRY(hipMemcpy(c.d_tab64, t64, sizeof(t64), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc((void **)&c.d_counters, 2 * MZ_NUM_COUNTERS * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void **)&c.counters.words, 2 * MZ_NUM_COUNTERS * sizeof(uint32_t)));
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, dev));
         c.cu_count = prop.multiProcessorCount;
@@ -91,142 +83,131 @@ int32_t mzh::ctx_for_current(DeviceCtx **out) {
 }
 
 namespace {
-// Per-launch device scratch, stream-ordered without the runtime's memory pools.  hipMallocAsync/hipFreeAsync was the
-// first implementation; on this stack (ROCm 7.2, gfx950) the second allocation of a process intermittently came back
-// with the kernels' and copies' early writes wiped (the whole block read as zero afterwards: 16 of 100 fresh processes,
-// profiles/r1/side_measurements.log), so buffers are plain hipMalloc memory cached here.  A buffer is handed out again
-// when the next launch is on the stream that used it last (stream order protects it) or when the event recorded behind
-// its last use has completed; otherwise another buffer is allocated, so concurrent streams never share scratch.
-// Identity of a stream for the "same stream => stream order protects the buffer" shortcut of the two caches below.
-// hipStreamPerThread is ONE handle value that names a different stream in every host thread: two threads must not
-// take each other for the same stream (they did for a day: a second thread's launch reused the work-queue head and the
-// record scratch of a kernel that was still running -- CRC errors in the two-thread drop-in test).
-hipStream_t stream_key(hipStream_t s) {
-    static thread_local char tls_marker;
-    return s == hipStreamPerThread ? (hipStream_t)(void *)&tls_marker : s;
-}
 
-} // namespace
-
-int32_t mzh::scratch_acquire(DeviceCtx *c, size_t bytes, hipStream_t s, int *slot, void **p) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    constexpr int kSlots = (int)(sizeof(c->scratch) / sizeof(c->scratch[0]));
-    int best = -1, empty = -1, victim = -1;
-    for (int i = 0; i < kSlots; i++) {
-        DeviceCtx::ScratchEnt &e = c->scratch[i];
-        if (!e.p) {
-            if (empty < 0) empty = i;
-            continue;
-        }
-        if (e.held) continue;
-        const bool done = !e.used || hipEventQuery(e.ev) == hipSuccess;
-        if (e.cap >= bytes && (done || e.last == stream_key(s))) {
-            if (best < 0 || e.cap < c->scratch[best].cap) best = i;
-        } else if (done && (victim < 0 || e.cap < c->scratch[victim].cap)) {
-            victim = i; // idle and too small
-        }
-    }
-    if (best < 0) {
-        int i = empty >= 0 ? empty : victim;
-        if (i < 0) { /* every buffer is busy on another stream: wait for one */
-            for (int k = 0; k < kSlots && i < 0; k++)
-                if (!c->scratch[k].held) i = k;
-            if (i < 0) {
-                snprintf(g_err, sizeof(g_err), "scratch: more than %d concurrent launches", kSlots);
-                return -104;
-            }
-            HIP_TRY(hipEventSynchronize(c->scratch[i].ev));
-        }
-        DeviceCtx::ScratchEnt &e = c->scratch[i];
-        if (e.p) {
-            HIP_TRY(hipFree(e.p));
-            e.p = nullptr;
-            e.cap = 0;
-        }
-        const size_t cap = (bytes + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
-        HIP_TRY(hipMalloc(&e.p, cap));
-        e.cap = cap;
-        e.used = false;
-        if (!e.ev) HIP_TRY(hipEventCreateWithFlags(&e.ev, hipEventDisableTiming));
-        best = i;
-    }
-    c->scratch[best].held = true;
-    *slot = best;
-    *p = c->scratch[best].p;
-    return 0;
-}
-
-int32_t mzh::scratch_release(DeviceCtx *c, int slot, hipStream_t s) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    DeviceCtx::ScratchEnt &e = c->scratch[slot];
-    e.held = false;
-    e.used = true;
-    e.last = stream_key(s);
-    HIP_TRY(hipEventRecord(e.ev, s));
-    return 0;
-}
-
-namespace {
-// The work-queue head of one launch.  The batch entry points are asynchronous on caller-supplied streams, so a counter
-// may only be handed out again when the launch that used it last is known to be over: the next launch is on the same
-// stream (stream order puts its memset behind that kernel) or the event recorded behind it has completed.  Otherwise
-// another slot is taken; with every slot busy on other streams the oldest one is waited for.
-struct CounterLease {
+// The prologue of a launcher: the current device's context, the caller's stream and, where the kernel has a work queue, its
+// zeroed heads -- given back (an event recorded behind the launch) when the launcher returns.
+struct Launch {
     DeviceCtx *c = nullptr;
     hipStream_t s = nullptr;
-    int idx = -1;
-    uint32_t *p = nullptr;
-    int32_t get(DeviceCtx *ctx, hipStream_t st) {
-        c = ctx;
-        s = st;
-        hipEvent_t wait_for = nullptr;
-        {
-            std::lock_guard<std::mutex> lk(g_mu);
-            for (uint32_t k = 0; k < MZ_NUM_COUNTERS && idx < 0; k++) {
-                const uint32_t i = (c->next_counter + k) % MZ_NUM_COUNTERS;
-                DeviceCtx::CounterSlot &e = c->cslots[i];
-                if (e.held) continue;
-                if (!e.used || e.last == stream_key(s) || hipEventQuery(e.ev) == hipSuccess) idx = (int)i;
-            }
-            if (idx < 0) { /* every counter is busy on another stream: take one that is not being set up right now and wait for its launch */
-                for (uint32_t k = 0; k < MZ_NUM_COUNTERS && idx < 0; k++) {
-                    const uint32_t i = (c->next_counter + k) % MZ_NUM_COUNTERS;
-                    if (!c->cslots[i].held) idx = (int)i;
-                }
-                if (idx < 0) {
-                    snprintf(g_err, sizeof(g_err), "more than %d launches being set up at once", MZ_NUM_COUNTERS);
-                    return -104;
-                }
-                wait_for = c->cslots[idx].ev;
-            }
-            c->cslots[idx].held = true; /* ours from here on: the wait below happens outside the lock (ADVICE r2) */
-            c->next_counter = (uint32_t)idx + 1u;
-        }
-        if (wait_for) HIP_TRY(hipEventSynchronize(wait_for));
-        p = c->d_counters + 2 * idx; /* two words per slot: the LZMA encoder's two kernels each have a head */
-        HIP_TRY(hipMemsetAsync(p, 0, 2 * sizeof(uint32_t), s));
-        return 0;
-    }
-    ~CounterLease() {
-        if (idx < 0) return;
-        std::lock_guard<std::mutex> lk(g_mu);
-        DeviceCtx::CounterSlot &e = c->cslots[idx];
-        if (!e.ev && hipEventCreateWithFlags(&e.ev, hipEventDisableTiming) != hipSuccess) e.ev = nullptr;
-        if (e.ev) (void)hipEventRecord(e.ev, s);
-        e.used = e.ev != nullptr;
-        e.last = stream_key(s);
-        e.held = false;
+    CounterLease head;
+    int32_t begin(void *stream, bool work_queue = true) {
+        const int32_t rc = ctx_for_current(&c);
+        if (rc) return rc;
+        s = (hipStream_t)stream;
+        return work_queue ? head.get(&c->counters, s) : 0;
     }
 };
 
+// The epilogue of a launcher that leased scratch: the lease is given back (its event recorded behind the launch) whatever
+// came of the launch; a launch error wins over a release error, which wins over success.
+int32_t launched(const char *what, hipError_t le, ScratchLease &sc) {
+    const int32_t rr = sc.release();
+    return le != hipSuccess ? fail(what, le) : rr;
+}
+
+// Persistent waves: the workgroups the work needs, at most the ones that are resident at once (fill the chip once).
+uint32_t resident_grid(uint64_t need, uint64_t resident) { return (uint32_t)(need < resident ? need : resident); }
+
+// The fields the argument structs of the batch kernels name alike; a.f = v where the struct has a field f, nothing otherwise.
+#define MZ_OPTIONAL_FIELD(f)                                                                               \
+    template <class A, class V> auto set_##f(A &a, V v, int) -> decltype((void)(a.f = v)) { a.f = v; } \
+    template <class A, class V> void set_##f(A &, V, long) {}
+MZ_OPTIONAL_FIELD(out_cap)
+MZ_OPTIONAL_FIELD(in_used)
+MZ_OPTIONAL_FIELD(crc)
+MZ_OPTIONAL_FIELD(tabs)
+MZ_OPTIONAL_FIELD(tab64)
+template <class A>
+void set_fields(A &a, const DeviceCtx *c, const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
+                const uint64_t *d_out_off, const uint32_t *d_out_cap, uint32_t n, uint32_t *d_out_len, uint32_t *d_in_used,
+                uint32_t *d_crc, int32_t *d_status) {
+    a.in = (const uint8_t *)d_in;
+    a.in_off = d_in_off;
+    a.in_len = d_in_len;
+    a.out = (uint8_t *)d_out;
+    a.out_off = d_out_off;
+    set_out_cap(a, d_out_cap, 0);
+    a.n = n;
+    a.out_len = d_out_len;
+    set_in_used(a, d_in_used, 0);
+    set_crc(a, d_crc, 0);
+    a.status = d_status;
+    set_tabs(a, c->d_tabs, 0);
+}
+
+template <class A>
+struct Kernel {
+    void (*fn)(A);
+    const char *name;
+};
+#define MZ_KERNEL(k) {k, #k}
+
 uint32_t grid_for(const DeviceCtx *c, uint32_t n) {
-    uint32_t wgs_needed = (n + MZ_WAVES_PER_WG - 1) / MZ_WAVES_PER_WG;
-    uint32_t resident = (uint32_t)(c->cu_count * c->inflate_wgs_per_cu); /* persistent waves: fill the chip once */
-    if (wgs_needed < 1) wgs_needed = 1;
+    const uint32_t wgs_needed = (n + MZ_WAVES_PER_WG - 1) / MZ_WAVES_PER_WG;
     /* (Round 4 measured "balanced rounds" -- just enough waves to fill ceil(n / resident) rounds evenly, 3128 instead of
      * 4096 for one rank's 12 500 entries at N = 8: 245 GiB/s against 279.  A nearly empty last round on a full chip beats
      * full rounds on three quarters of it: profiles/r4/ab_balanced_rounds.log.) */
-    return wgs_needed < resident ? wgs_needed : resident;
+    return resident_grid(wgs_needed ? wgs_needed : 1u, (uint32_t)(c->cu_count * c->inflate_wgs_per_cu));
+}
+
+// ZipCrypto, both directions: a lane per entry; `a` arrives with the fields only one direction has
+template <class A>
+int32_t pkcrypt_batch(A &a, void (*kernel)(A), const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
+                             const uint64_t *d_out_off, uint32_t n, const uint8_t *password, uint32_t password_len,
+                             const uint32_t *d_verify, uint32_t *d_out_len, int32_t *d_status, void *stream) {
+    if (!password) return MZ_CRYPT_PARAM_ERROR;
+    if (n == 0) return 0;
+    Launch L;
+    const int32_t rc = L.begin(stream, false);
+    if (rc) return rc;
+    set_fields(a, L.c, d_in, d_in_off, d_in_len, d_out, d_out_off, nullptr, n, d_out_len, nullptr, nullptr, d_status);
+    uint32_t keys[3];
+    mz_pk_init_keys_host(password, password_len, keys);
+    a.k0 = keys[0];
+    a.k1 = keys[1];
+    a.k2 = keys[2];
+    a.verify = d_verify;
+    hipLaunchKernelGGL(kernel, dim3((n + 255) / 256), dim3(256), 0, L.s, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// WinZip-AES, both directions: the entries' keys (four lanes an entry), CTR over the payloads (the work queue), the HMAC
+// a lane per entry -- on the way in behind the CTR kernel: it authenticates the ciphertext that kernel wrote
+template <class A>
+int32_t wzaes_batch(A &a, const Kernel<A> (&k)[3], const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                           const uint8_t *d_strength, void *d_out, const uint64_t *d_out_off, uint32_t n, const uint8_t *password,
+                           uint32_t password_len, uint32_t *d_out_len, int32_t *d_status, void *stream) {
+    if (!password || password_len > MZ_WZAES_PW_MAX) return MZ_CRYPT_PARAM_ERROR;
+    if (n == 0) return 0;
+    if (n > 0x3FFFFFFFu) return MZ_CRYPT_PARAM_ERROR; /* four lane slots per entry in a 32-bit thread index */
+    Launch L;
+    int32_t rc = L.begin(stream);
+    if (rc) return rc;
+    set_fields(a, L.c, d_in, d_in_off, d_in_len, d_out, d_out_off, nullptr, n, d_out_len, nullptr, nullptr, d_status);
+    a.strength = d_strength;
+    a.password_len = password_len;
+    memset(a.password, 0, sizeof(a.password));
+    memcpy(a.password, password, password_len);
+    a.counter = L.head.p;
+    ScratchLease sc;
+    rc = sc.get(&L.c->scratch, (size_t)n * sizeof(mz_wzaes_entry_keys), L.s);
+    if (rc) return rc;
+    a.keys = (mz_wzaes_entry_keys *)sc.p;
+    int at = 0;
+    hipLaunchKernelGGL(k[0].fn, dim3((uint32_t)(((uint64_t)n * 4u + 255u) / 256u)), dim3(256), 0, L.s, a);
+    hipError_t le = hipGetLastError();
+    if (le == hipSuccess) {
+        at = 1;
+        hipLaunchKernelGGL(k[1].fn, dim3(grid_for(L.c, n)), dim3(MZ_WAVES_PER_WG * 64), 0, L.s, a);
+        le = hipGetLastError();
+    }
+    if (le == hipSuccess) {
+        at = 2;
+        hipLaunchKernelGGL(k[2].fn, dim3((n + 255) / 256), dim3(256), 0, L.s, a);
+        le = hipGetLastError();
+    }
+    return launched(k[at].name, le, sc);
 }
 
 } // namespace
@@ -255,133 +236,77 @@ int32_t mzhip_inflate_resume_batch(const void *d_in, const uint64_t *d_in_off, c
                                    mzhip_inflate_state *d_stop, void *stream) {
     static_assert(sizeof(mzhip_inflate_state) == sizeof(mz_inflate_state), "mzhip.h and inflate_core.h describe the same four words");
     if (n == 0) return 0;
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
+    Launch L;
+    int32_t rc = L.begin(stream);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
     InflateArgs a;
-    a.in = (const uint8_t *)d_in;
-    a.in_off = d_in_off;
-    a.in_len = d_in_len;
-    a.out = (uint8_t *)d_out;
-    a.out_off = d_out_off;
-    a.out_cap = d_out_cap;
-    a.n = n;
-    a.out_len = d_out_len;
-    a.in_used = d_in_used;
-    a.crc = d_crc;
-    a.status = d_status;
-    CounterLease lease;
-    rc = lease.get(c, s);
-    if (rc) return rc;
-    a.counter = lease.p;
-    a.tabs = c->d_tabs;
-    const size_t lds = MZ_CRC_TAB_BYTES + MZ_WAVES_PER_WG * MZ_LDS_STRIDE;
-    const uint32_t grid = grid_for(c, n);
-    a.rec = nullptr;
+    set_fields(a, L.c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, d_in_used, d_crc, d_status);
+    a.counter = L.head.p;
     a.resume = (const mz_inflate_state *)d_resume;
     a.stop = (mz_inflate_state *)d_stop;
-    int slot = -1;
-    { /* the step records of the chase window: MZ_REC_BYTES per wave of the launch (176 KiB x 4096 resident waves at most) */
-        void *scratch = nullptr;
-        rc = scratch_acquire(c, (size_t)grid * MZ_WAVES_PER_WG * MZ_REC_BYTES + 1024, s, &slot, &scratch);
-        if (rc) return rc;
-        a.rec = (uint8_t *)scratch;
-    }
-    if (a.resume || a.stop) hipLaunchKernelGGL(k_inflate_batch<true>, dim3(grid), dim3(MZ_WAVES_PER_WG * 64), lds, s, a);
-    else hipLaunchKernelGGL(k_inflate_batch<false>, dim3(grid), dim3(MZ_WAVES_PER_WG * 64), lds, s, a);
-    const hipError_t le = hipGetLastError();
-    if (slot >= 0) {
-        const int32_t rr = scratch_release(c, slot, s);
-        if (rr && le == hipSuccess) return rr;
-    }
-    if (le != hipSuccess) return fail("k_inflate_batch", le);
-    return 0;
+    const size_t lds = MZ_CRC_TAB_BYTES + MZ_WAVES_PER_WG * MZ_LDS_STRIDE;
+    const uint32_t grid = grid_for(L.c, n);
+    ScratchLease sc; /* the step records of the chase window: MZ_REC_BYTES per wave of the launch (176 KiB x 4096 resident waves at most) */
+    rc = sc.get(&L.c->scratch, (size_t)grid * MZ_WAVES_PER_WG * MZ_REC_BYTES + 1024, L.s);
+    if (rc) return rc;
+    a.rec = (uint8_t *)sc.p;
+    if (a.resume || a.stop) hipLaunchKernelGGL(k_inflate_batch<true>, dim3(grid), dim3(MZ_WAVES_PER_WG * 64), lds, L.s, a);
+    else hipLaunchKernelGGL(k_inflate_batch<false>, dim3(grid), dim3(MZ_WAVES_PER_WG * 64), lds, L.s, a);
+    return launched("k_inflate_batch", hipGetLastError(), sc);
 }
 
-int32_t mzhip_crc32_batch(const void *d_buf, const uint64_t *d_off, const uint32_t *d_len, uint32_t n,
-                          const uint32_t *d_init, uint32_t *d_crc, void *stream) {
+// CRC-32 (d_init: the values to go on from, or null) and Adler-32 of n byte ranges, a wave each
+static int32_t checksum_batch(void (*kernel)(CrcArgs), const void *d_buf, const uint64_t *d_off, const uint32_t *d_len, uint32_t n,
+                              const uint32_t *d_init, uint32_t *d_sum, void *stream) {
     if (n == 0) return 0;
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
+    Launch L;
+    const int32_t rc = L.begin(stream);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
     CrcArgs a;
     a.buf = (const uint8_t *)d_buf;
     a.off = d_off;
     a.len = d_len;
     a.n = n;
     a.init = d_init;
-    a.crc = d_crc;
-    CounterLease lease;
-    rc = lease.get(c, s);
-    if (rc) return rc;
-    a.counter = lease.p;
-    a.tabs = c->d_tabs;
-    hipLaunchKernelGGL(k_crc32_batch, dim3(grid_for(c, n)), dim3(MZ_WAVES_PER_WG * 64), 0, s, a);
+    a.crc = d_sum;
+    a.counter = L.head.p;
+    a.tabs = L.c->d_tabs;
+    hipLaunchKernelGGL(kernel, dim3(grid_for(L.c, n)), dim3(MZ_WAVES_PER_WG * 64), 0, L.s, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
+int32_t mzhip_crc32_batch(const void *d_buf, const uint64_t *d_off, const uint32_t *d_len, uint32_t n,
+                          const uint32_t *d_init, uint32_t *d_crc, void *stream) {
+    return checksum_batch(k_crc32_batch, d_buf, d_off, d_len, n, d_init, d_crc, stream);
+}
+
 int32_t mzhip_adler32_batch(const void *d_buf, const uint64_t *d_off, const uint32_t *d_len, uint32_t n,
                             uint32_t *d_adler, void *stream) {
-    if (n == 0) return 0;
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    CrcArgs a;
-    a.buf = (const uint8_t *)d_buf;
-    a.off = d_off;
-    a.len = d_len;
-    a.n = n;
-    a.init = nullptr;
-    a.crc = d_adler;
-    CounterLease lease;
-    rc = lease.get(c, s);
-    if (rc) return rc;
-    a.counter = lease.p;
-    a.tabs = c->d_tabs;
-    hipLaunchKernelGGL(k_adler32_batch, dim3(grid_for(c, n)), dim3(MZ_WAVES_PER_WG * 64), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return checksum_batch(k_adler32_batch, d_buf, d_off, d_len, n, nullptr, d_adler, stream);
 }
 
 static int32_t lzma_family_batch(int xz, const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
                                  const uint64_t *d_out_off, const uint32_t *d_out_cap, const int64_t *d_max_out, uint32_t n,
                                  uint32_t *d_out_len, uint32_t *d_in_used, uint32_t *d_crc, int32_t *d_status, void *stream) {
     if (n == 0) return 0;
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
+    Launch L;
+    int32_t rc = L.begin(stream);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
+    DeviceCtx *c = L.c;
+    hipStream_t s = L.s;
     LzmaArgs a;
-    a.in = (const uint8_t *)d_in;
-    a.in_off = d_in_off;
-    a.in_len = d_in_len;
-    a.out = (uint8_t *)d_out;
-    a.out_off = d_out_off;
-    a.out_cap = d_out_cap;
+    set_fields(a, c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, d_in_used, d_crc, d_status);
     a.max_out = d_max_out;
-    a.n = n;
-    a.out_len = d_out_len;
-    a.in_used = d_in_used;
-    a.crc = d_crc;
-    a.status = d_status;
-    CounterLease lease;
-    rc = lease.get(c, s);
-    if (rc) return rc;
-    a.counter = lease.p;
-    a.tabs = c->d_tabs;
+    a.counter = L.head.p;
     a.tab64 = c->d_tab64;
     /* 16 KiB LDS per wave -> 10 single-wave workgroups per CU (K3); 17.6 KiB -> 8 (.xz) */
     uint32_t resident = (uint32_t)c->cu_count * (xz ? 8u : 10u);
 #ifdef MZ_LZMA_RESIDENT /* measurement builds: single-wave workgroups per CU that really fit (LDS and registers) */
     if (!xz) resident = (uint32_t)c->cu_count * MZ_LZMA_RESIDENT;
 #endif
-    uint32_t grid = n < resident ? n : resident;
-    int slot = -1;
-    void *scratch = nullptr; /* 12 KiB per resident wave: the literal model's upper half for streams with lc + lp = 4 */
+    const uint32_t grid = resident_grid(n, resident);
+    ScratchLease sc; /* 12 KiB per resident wave: the literal model's upper half for streams with lc + lp = 4 */
     a.sprobs = nullptr;
     a.retry_list = nullptr;
     a.retry_n = nullptr;
@@ -396,15 +321,15 @@ static int32_t lzma_family_batch(int xz, const void *d_in, const uint64_t *d_in_
 #define MZ_LZMA_SLOT_WGS 4u /* workgroups of four waves per CU (measurement builds: 1 or 2 -- how fast is a stream's chain of decisions
                                when fewer waves share the SIMD's issue port?  profiles/r6/README.md, K3) */
 #endif
-        const uint32_t res_s = (uint32_t)c->cu_count * MZ_LZMA_SLOT_WGS; /* workgroups of four waves */
-        const uint32_t grid_s = (n + 3u) / 4u < res_s ? (n + 3u) / 4u : res_s;
+        const uint32_t grid_s = resident_grid((n + 3u) / 4u, (uint32_t)c->cu_count * MZ_LZMA_SLOT_WGS); /* workgroups of four waves */
         const size_t sp_bytes = (size_t)grid_s * 4u * MZ_LZMA_SPROBS * sizeof(uint16_t);
         const size_t xp_bytes = (size_t)grid * MZ_LZMA_XPROBS * sizeof(uint16_t);
-        rc = scratch_acquire(c, sp_bytes + xp_bytes + (size_t)n * 4 + 256, s, &slot, &scratch);
+        rc = sc.get(&c->scratch, sp_bytes + xp_bytes + (size_t)n * 4 + 256, s);
         if (rc) return rc;
+        uint8_t *scratch = (uint8_t *)sc.p;
         a.sprobs = (uint16_t *)scratch;
-        a.xprobs = (uint16_t *)((uint8_t *)scratch + sp_bytes);
-        uint32_t *list = (uint32_t *)((uint8_t *)scratch + sp_bytes + xp_bytes);
+        a.xprobs = (uint16_t *)(scratch + sp_bytes);
+        uint32_t *list = (uint32_t *)(scratch + sp_bytes + xp_bytes);
         a.retry_list = list + 64;
         a.retry_n = list; /* one word, zeroed with the launch */
         hipError_t he = hipMemsetAsync(list, 0, 256, s);
@@ -413,25 +338,20 @@ static int32_t lzma_family_batch(int xz, const void *d_in, const uint64_t *d_in_
             he = hipGetLastError();
         }
         if (he == hipSuccess) {
-            a.counter = lease.p + 1; /* the second head of the lease */
+            a.counter = L.head.p + 1; /* the second head of the lease */
             hipLaunchKernelGGL(k_lzma_batch, dim3(grid), dim3(64), 0, s, a);
             he = hipGetLastError();
         }
-        rc = scratch_release(c, slot, s);
-        if (he != hipSuccess) return fail("k_lzma_slot_batch", he);
-        return rc;
+        return launched("k_lzma_slot_batch", he, sc);
     }
-    rc = scratch_acquire(c, (size_t)grid * MZ_LZMA_XPROBS * sizeof(uint16_t), s, &slot, &scratch);
+    rc = sc.get(&c->scratch, (size_t)grid * MZ_LZMA_XPROBS * sizeof(uint16_t), s);
     if (rc) return rc;
-    a.xprobs = (uint16_t *)scratch;
+    a.xprobs = (uint16_t *)sc.p;
     if (xz)
         hipLaunchKernelGGL(k_xz_batch, dim3(grid), dim3(64), 0, s, a);
     else
         hipLaunchKernelGGL(k_lzma_batch, dim3(grid), dim3(64), 0, s, a);
-    const hipError_t le = hipGetLastError();
-    rc = scratch_release(c, slot, s);
-    if (le != hipSuccess) return fail("k_lzma_batch", le);
-    return rc;
+    return launched("k_lzma_batch", hipGetLastError(), sc);
 }
 
 int32_t mzhip_lzma_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
@@ -456,10 +376,7 @@ int32_t mzhip_xz_batch(const void *d_in, const uint64_t *d_in_off, const uint32_
  * scratch. */
 #define MZ_BZ_WAVES_PER_CU 8u
 
-static uint32_t bzip2_grid(const DeviceCtx *c, uint32_t n) {
-    const uint32_t resident = (uint32_t)c->cu_count * MZ_BZ_WAVES_PER_CU;
-    return n < resident ? n : resident;
-}
+static uint32_t bzip2_grid(const DeviceCtx *c, uint32_t n) { return resident_grid(n, (uint32_t)c->cu_count * MZ_BZ_WAVES_PER_CU); }
 
 void mzhip_bzip2_launch_geometry(uint32_t n, uint32_t *grid, uint64_t *scratch_bytes) {
     DeviceCtx *c = nullptr;
@@ -473,38 +390,19 @@ int32_t mzhip_bzip2_batch(const void *d_in, const uint64_t *d_in_off, const uint
                           const uint64_t *d_out_off, const uint32_t *d_out_cap, uint32_t n, uint32_t *d_out_len,
                           uint32_t *d_in_used, uint32_t *d_crc, int32_t *d_status, void *stream) {
     if (n == 0) return 0;
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
+    Launch L;
+    int32_t rc = L.begin(stream);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
     Bzip2Args a;
-    a.in = (const uint8_t *)d_in;
-    a.in_off = d_in_off;
-    a.in_len = d_in_len;
-    a.out = (uint8_t *)d_out;
-    a.out_off = d_out_off;
-    a.out_cap = d_out_cap;
-    a.n = n;
-    a.out_len = d_out_len;
-    a.in_used = d_in_used;
-    a.crc = d_crc;
-    a.status = d_status;
-    CounterLease lease;
-    rc = lease.get(c, s);
+    set_fields(a, L.c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, d_in_used, d_crc, d_status);
+    a.counter = L.head.p;
+    const uint32_t grid = bzip2_grid(L.c, n);
+    ScratchLease sc;
+    rc = sc.get(&L.c->scratch, (size_t)grid * MZ_BZ_SCRATCH_BYTES, L.s);
     if (rc) return rc;
-    a.counter = lease.p;
-    a.tabs = c->d_tabs;
-    const uint32_t grid = bzip2_grid(c, n);
-    int slot = -1;
-    void *scratch = nullptr;
-    rc = scratch_acquire(c, (size_t)grid * MZ_BZ_SCRATCH_BYTES, s, &slot, &scratch);
-    if (rc) return rc;
-    a.scratch = (uint8_t *)scratch;
-    hipLaunchKernelGGL(k_bzip2_batch, dim3(grid), dim3(64), 0, s, a);
-    const hipError_t le = hipGetLastError();
-    rc = scratch_release(c, slot, s);
-    if (le != hipSuccess) return fail("k_bzip2_batch", le);
-    return rc;
+    a.scratch = (uint8_t *)sc.p;
+    hipLaunchKernelGGL(k_bzip2_batch, dim3(grid), dim3(64), 0, L.s, a);
+    return launched("k_bzip2_batch", hipGetLastError(), sc);
 }
 
 int32_t mzhip_sha_batch(const void *d_buf, const uint64_t *d_off, const uint32_t *d_len, uint32_t n, uint32_t algorithm,
@@ -538,162 +436,36 @@ int32_t mzhip_sha_batch(const void *d_buf, const uint64_t *d_off, const uint32_t
 int32_t mzhip_pkcrypt_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
                             const uint64_t *d_out_off, uint32_t n, const uint8_t *password, uint32_t password_len,
                             const uint32_t *d_verify, uint32_t *d_out_len, int32_t *d_status, void *stream) {
-    if (!password) return MZ_CRYPT_PARAM_ERROR;
-    if (n == 0) return 0;
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
     PkcryptArgs a;
-    a.in = (const uint8_t *)d_in;
-    a.in_off = d_in_off;
-    a.in_len = d_in_len;
-    a.out = (uint8_t *)d_out;
-    a.out_off = d_out_off;
-    a.n = n;
-    uint32_t keys[3];
-    mz_pk_init_keys_host(password, password_len, keys);
-    a.k0 = keys[0];
-    a.k1 = keys[1];
-    a.k2 = keys[2];
-    a.verify = d_verify;
-    a.out_len = d_out_len;
-    a.status = d_status;
-    a.tabs = c->d_tabs;
-    hipLaunchKernelGGL(k_pkcrypt_batch, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return pkcrypt_batch(a, k_pkcrypt_batch, d_in, d_in_off, d_in_len, d_out, d_out_off, n, password, password_len, d_verify,
+                         d_out_len, d_status, stream);
 }
 
 int32_t mzhip_wzaes_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, const uint8_t *d_strength,
                           void *d_out, const uint64_t *d_out_off, uint32_t n, const uint8_t *password, uint32_t password_len,
                           uint32_t *d_out_len, int32_t *d_status, void *stream) {
-    if (!password || password_len > MZ_WZAES_PW_MAX) return MZ_CRYPT_PARAM_ERROR;
-    if (n == 0) return 0;
-    if (n > 0x3FFFFFFFu) return MZ_CRYPT_PARAM_ERROR; /* four lane slots per entry in a 32-bit thread index */
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
+    static const Kernel<WzaesArgs> k[3] = {MZ_KERNEL(k_wzaes_keys), MZ_KERNEL(k_wzaes_ctr), MZ_KERNEL(k_wzaes_auth)};
     WzaesArgs a;
-    a.in = (const uint8_t *)d_in;
-    a.in_off = d_in_off;
-    a.in_len = d_in_len;
-    a.strength = d_strength;
-    a.out = (uint8_t *)d_out;
-    a.out_off = d_out_off;
-    a.n = n;
-    a.password_len = password_len;
-    memset(a.password, 0, sizeof(a.password));
-    memcpy(a.password, password, password_len);
-    a.out_len = d_out_len;
-    a.status = d_status;
-    CounterLease lease;
-    rc = lease.get(c, s);
-    if (rc) return rc;
-    a.counter = lease.p;
-    int slot = -1;
-    void *scratch = nullptr;
-    rc = scratch_acquire(c, (size_t)n * sizeof(mz_wzaes_entry_keys), s, &slot, &scratch);
-    if (rc) return rc;
-    a.keys = (mz_wzaes_entry_keys *)scratch;
-    const char *what = "k_wzaes_keys";
-    hipLaunchKernelGGL(k_wzaes_keys, dim3((uint32_t)(((uint64_t)n * 4u + 255u) / 256u)), dim3(256), 0, s, a);
-    hipError_t le = hipGetLastError();
-    if (le == hipSuccess) {
-        what = "k_wzaes_ctr";
-        hipLaunchKernelGGL(k_wzaes_ctr, dim3(grid_for(c, n)), dim3(MZ_WAVES_PER_WG * 64), 0, s, a);
-        le = hipGetLastError();
-    }
-    if (le == hipSuccess) {
-        what = "k_wzaes_auth";
-        hipLaunchKernelGGL(k_wzaes_auth, dim3((n + 255) / 256), dim3(256), 0, s, a);
-        le = hipGetLastError();
-    }
-    rc = scratch_release(c, slot, s);
-    if (le != hipSuccess) return fail(what, le);
-    return rc;
+    return wzaes_batch(a, k, d_in, d_in_off, d_in_len, d_strength, d_out, d_out_off, n, password, password_len, d_out_len, d_status, stream);
 }
 
 int32_t mzhip_pkcrypt_encrypt_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
                                     const uint64_t *d_out_off, uint32_t n, const uint8_t *password, uint32_t password_len,
                                     const uint32_t *d_verify, const uint8_t *d_header, uint32_t *d_out_len, int32_t *d_status,
                                     void *stream) {
-    if (!password) return MZ_CRYPT_PARAM_ERROR;
-    if (n == 0) return 0;
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
     PkcryptEncArgs a;
-    a.in = (const uint8_t *)d_in;
-    a.in_off = d_in_off;
-    a.in_len = d_in_len;
-    a.out = (uint8_t *)d_out;
-    a.out_off = d_out_off;
-    a.n = n;
-    uint32_t keys[3];
-    mz_pk_init_keys_host(password, password_len, keys);
-    a.k0 = keys[0];
-    a.k1 = keys[1];
-    a.k2 = keys[2];
-    a.verify = d_verify;
     a.header = d_header;
-    a.out_len = d_out_len;
-    a.status = d_status;
-    a.tabs = c->d_tabs;
-    hipLaunchKernelGGL(k_pkcrypt_enc_batch, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return pkcrypt_batch(a, k_pkcrypt_enc_batch, d_in, d_in_off, d_in_len, d_out, d_out_off, n, password, password_len,
+                         d_verify, d_out_len, d_status, stream);
 }
 
 int32_t mzhip_wzaes_encrypt_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, const uint8_t *d_strength,
                                   const uint8_t *d_salt, void *d_out, const uint64_t *d_out_off, uint32_t n, const uint8_t *password,
                                   uint32_t password_len, uint32_t *d_out_len, int32_t *d_status, void *stream) {
-    if (!password || password_len > MZ_WZAES_PW_MAX) return MZ_CRYPT_PARAM_ERROR;
-    if (n == 0) return 0;
-    if (n > 0x3FFFFFFFu) return MZ_CRYPT_PARAM_ERROR; /* four lane slots per entry in a 32-bit thread index */
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
+    static const Kernel<WzaesEncArgs> k[3] = {MZ_KERNEL(k_wzaes_enc_keys), MZ_KERNEL(k_wzaes_enc_ctr), MZ_KERNEL(k_wzaes_enc_auth)};
     WzaesEncArgs a;
-    a.in = (const uint8_t *)d_in;
-    a.in_off = d_in_off;
-    a.in_len = d_in_len;
-    a.strength = d_strength;
     a.salt = d_salt;
-    a.out = (uint8_t *)d_out;
-    a.out_off = d_out_off;
-    a.n = n;
-    a.password_len = password_len;
-    memset(a.password, 0, sizeof(a.password));
-    memcpy(a.password, password, password_len);
-    a.out_len = d_out_len;
-    a.status = d_status;
-    CounterLease lease;
-    rc = lease.get(c, s);
-    if (rc) return rc;
-    a.counter = lease.p;
-    int slot = -1;
-    void *scratch = nullptr;
-    rc = scratch_acquire(c, (size_t)n * sizeof(mz_wzaes_entry_keys), s, &slot, &scratch);
-    if (rc) return rc;
-    a.keys = (mz_wzaes_entry_keys *)scratch;
-    const char *what = "k_wzaes_enc_keys";
-    hipLaunchKernelGGL(k_wzaes_enc_keys, dim3((uint32_t)(((uint64_t)n * 4u + 255u) / 256u)), dim3(256), 0, s, a);
-    hipError_t le = hipGetLastError();
-    if (le == hipSuccess) {
-        what = "k_wzaes_enc_ctr";
-        hipLaunchKernelGGL(k_wzaes_enc_ctr, dim3(grid_for(c, n)), dim3(MZ_WAVES_PER_WG * 64), 0, s, a);
-        le = hipGetLastError();
-    }
-    if (le == hipSuccess) { /* behind the CTR kernel: it authenticates the ciphertext that kernel wrote */
-        what = "k_wzaes_enc_auth";
-        hipLaunchKernelGGL(k_wzaes_enc_auth, dim3((n + 255) / 256), dim3(256), 0, s, a);
-        le = hipGetLastError();
-    }
-    rc = scratch_release(c, slot, s);
-    if (le != hipSuccess) return fail(what, le);
-    return rc;
+    return wzaes_batch(a, k, d_in, d_in_off, d_in_len, d_strength, d_out, d_out_off, n, password, password_len, d_out_len, d_status, stream);
 }
 
 int32_t mzhip_deflate_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
@@ -717,28 +489,16 @@ int32_t mzh::deflate_batch_launch(const void *d_in, const uint64_t *d_in_off, co
                                   void *stream) {
     if (n == 0) return 0;
     if (window_log2 < 9 || window_log2 > 15) return MZHIP_STATUS_UNSUPPORTED;
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
+    Launch L;
+    int32_t rc = L.begin(stream);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
+    DeviceCtx *c = L.c;
+    hipStream_t s = L.s;
     DeflateArgs a;
-    a.in = (const uint8_t *)d_in;
-    a.in_off = d_in_off;
-    a.in_len = d_in_len;
-    a.out = (uint8_t *)d_out;
-    a.out_off = d_out_off;
-    a.out_cap = d_out_cap;
+    set_fields(a, c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, nullptr, d_crc, d_status);
     a.final_flag = d_final;
     a.warm = d_warm;
-    a.n = n;
-    a.out_len = d_out_len;
-    a.crc = d_crc;
-    a.status = d_status;
-    CounterLease lease;
-    rc = lease.get(c, s);
-    if (rc) return rc;
-    a.counter = lease.p;
-    a.tabs = c->d_tabs;
+    a.counter = L.head.p;
     /* compression classes (mz_strm_zlib.c:87 hands `level` to deflateInit2): 0-3 fast = one candidate per hash bucket,
      * everything else (4-9, and -1 = Z_DEFAULT_COMPRESSION) = MZ_DEF_WAYS_BEST candidates + a two-position lazy rule */
     a.ways = (level >= 0 && level <= 3) ? 1u : MZ_DEF_WAYS_BEST;
@@ -755,17 +515,15 @@ int32_t mzh::deflate_batch_launch(const void *d_in, const uint64_t *d_in_off, co
     }
     a.max_dist = (1u << window_log2) - 262u; /* zlib's MAX_DIST(s) = w_size - MIN_LOOKAHEAD */
     const size_t lds = MZ_CRC_TAB_BYTES + MZ_WAVES_PER_WG * (MZ_DEF_LDS_STRIDE + (a.ways > 1u ? MZ_DEF_XHEAD_BYTES : 0));
-    uint32_t wgs = (n + MZ_WAVES_PER_WG - 1) / MZ_WAVES_PER_WG;
 #ifndef MZ_DEF_WGS
 #define MZ_DEF_WGS 4u /* workgroups of the fast class per CU (measurement builds: 1, 2 -- traffic against residency, profiles/r6/README.md K4) */
 #endif
-    uint32_t resident = (uint32_t)c->cu_count * (a.ways > 1u ? 1u : MZ_DEF_WGS); /* 38.3 / 134 KiB LDS per workgroup -> 4 / 1 per CU */
-    const uint32_t grid = wgs < resident ? wgs : resident;
-    int slot = -1;
-    void *scratch = nullptr; /* one token block per resident wave */
-    rc = scratch_acquire(c, (size_t)grid * MZ_WAVES_PER_WG * MZ_DEF_BLOCK * sizeof(uint32_t), s, &slot, &scratch);
+    /* 38.3 / 134 KiB LDS per workgroup -> 4 / 1 per CU */
+    const uint32_t grid = resident_grid((n + MZ_WAVES_PER_WG - 1) / MZ_WAVES_PER_WG, (uint32_t)c->cu_count * (a.ways > 1u ? 1u : MZ_DEF_WGS));
+    ScratchLease sc; /* one token block per resident wave */
+    rc = sc.get(&c->scratch, (size_t)grid * MZ_WAVES_PER_WG * MZ_DEF_BLOCK * sizeof(uint32_t), s);
     if (rc) return rc;
-    a.tok = (uint32_t *)scratch;
+    a.tok = (uint32_t *)sc.p;
     if (a.parse) hipLaunchKernelGGL(k_deflate_cost_batch, dim3(grid), dim3(MZ_WAVES_PER_WG * 64), lds, s, a);
     else hipLaunchKernelGGL(k_deflate_batch, dim3(grid), dim3(MZ_WAVES_PER_WG * 64), lds, s, a);
     hipError_t le = hipGetLastError();
@@ -776,9 +534,7 @@ int32_t mzh::deflate_batch_launch(const void *d_in, const uint64_t *d_in_off, co
         hipLaunchKernelGGL(k_deflate_batch, dim3(grid), dim3(MZ_WAVES_PER_WG * 64), MZ_CRC_TAB_BYTES + MZ_WAVES_PER_WG * MZ_DEF_LDS_STRIDE, s, a);
         le = hipGetLastError();
     }
-    rc = scratch_release(c, slot, s);
-    if (le != hipSuccess) return fail("k_deflate_batch", le);
-    return rc;
+    return launched("k_deflate_batch", le, sc);
 }
 
 namespace {
@@ -791,15 +547,44 @@ void launch_lz_parse(DeviceCtx *c, hipStream_t s, LzmaEncArgs &a, uint32_t chain
     const size_t items = (size_t)a.n * a.maxb;
     const uint32_t wgs = (uint32_t)((items + MZ_WAVES_PER_WG - 1) / MZ_WAVES_PER_WG);
     const size_t lds = MZ_WAVES_PER_WG * (sizeof(mz_lz_tok_lds) + (a.ways > 1u ? MZ_DEF_XHEAD_BYTES : 0));
-    uint32_t resident = (uint32_t)c->cu_count * (a.ways > 1u ? 1u : 4u); /* 128 KiB (32 KiB) of LDS per workgroup */
-    hipLaunchKernelGGL(k_lz_tokenize_batch, dim3(wgs < resident ? wgs : resident), dim3(MZ_WAVES_PER_WG * 64), lds, s, a);
+    const uint32_t cus = (uint32_t)c->cu_count; /* 128 KiB (32 KiB) of LDS per workgroup: 1 (4) per CU */
+    hipLaunchKernelGGL(k_lz_tokenize_batch, dim3(resident_grid(wgs, cus * (a.ways > 1u ? 1u : 4u))), dim3(MZ_WAVES_PER_WG * 64), lds, s, a);
     if (a.ways > 1u && hipGetLastError() != hipSuccess) { /* 128 KiB of LDS per workgroup refused after all */
         c->big_lds_tok.store(-1, std::memory_order_release);
         a.ways = 1u;
-        resident = (uint32_t)c->cu_count * 4u;
-        hipLaunchKernelGGL(k_lz_tokenize_batch, dim3(wgs < resident ? wgs : resident), dim3(MZ_WAVES_PER_WG * 64),
+        hipLaunchKernelGGL(k_lz_tokenize_batch, dim3(resident_grid(wgs, cus * 4u)), dim3(MZ_WAVES_PER_WG * 64),
                            MZ_WAVES_PER_WG * sizeof(mz_lz_tok_lds), s, a);
     }
+}
+/* preset (mz_strm_lzma.c:81 hands COMPRESS_LEVEL to lzma_lzma_preset): 0-3 -> one hash candidate per position, 4-9 and
+ * the default (-1 = 6) -> MZ_DEF_WAYS_BEST candidates + the two-position lazy rule, as K4's classes -- where the device
+ * grants the tokenizer its 128 KiB of dynamic LDS per workgroup, the one-candidate class where it does not */
+void set_lz_class(DeviceCtx *c, LzmaEncArgs &a, int32_t preset) {
+    a.ways = (preset >= 0 && preset <= 3) ? 1u : MZ_DEF_WAYS_BEST;
+    a.far_depth = MZ_LZE_DEPTH_FOR_PRESET(preset);
+    if (a.ways > 1u && !big_lds_ok(c->big_lds_tok, (const void *)k_lz_tokenize_batch, MZ_WAVES_PER_WG * (sizeof(mz_lz_tok_lds) + MZ_DEF_XHEAD_BYTES)))
+        a.ways = 1u;
+}
+/* ONE stream of `maxb` blocks for the host-buffer writers, parsed: entry 0's words are the meta block's at `base` (offsets
+ * from there), `tok` has room for the tokens, the chain pass's links (as many words again) and its table, the token counts
+ * and three counters; skip_blocks of history in front are linked (the segment's links point into them), not parsed */
+template <class Meta>
+int32_t lz_parse_one_stream(DeviceCtx *c, hipStream_t s, LzmaEncArgs &a, uint8_t *base, Meta *dm, uint32_t maxb, uint32_t skip_blocks,
+                            int32_t preset, uint32_t *tok) {
+    set_fields(a, c, base, &dm->in_off, &dm->in_len, base, &dm->out_off, &dm->out_cap, 1, &dm->out_len, nullptr, &dm->crc, &dm->status);
+    a.mode = nullptr;
+    a.maxb = maxb;
+    set_lz_class(c, a, preset);
+    a.tok = tok;
+    a.links = a.tok + (size_t)maxb * MZ_DEF_BLOCK;
+    a.chain_head = a.links + (size_t)maxb * MZ_DEF_BLOCK;
+    a.skip_blocks = skip_blocks;
+    a.ntok = a.chain_head + ((size_t)1 << MZ_LZE_FAR_HBITS);
+    a.counter = a.ntok + maxb;
+    HIP_TRY(hipMemsetAsync(a.counter, 0, 3 * sizeof(uint32_t), s));
+    if (maxb <= 1u) a.links = nullptr;
+    launch_lz_parse(c, s, a, 1u);
+    return 0;
 }
 } // namespace
 extern "C" {
@@ -811,67 +596,40 @@ int32_t mzhip_lzma_encode_batch(const void *d_in, const uint64_t *d_in_off, cons
                                           d_out_len, d_crc, d_status, stream);
 }
 
-/* preset (mz_strm_lzma.c:81 hands COMPRESS_LEVEL to lzma_lzma_preset): 0-3 -> one hash candidate per position, 4-9 and
- * the default (-1 = 6) -> MZ_DEF_WAYS_BEST candidates + the two-position lazy rule, as K4's classes */
 int32_t mzhip_lzma_encode_batch_preset(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, uint32_t max_in_len,
                                        void *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap, const uint8_t *d_mode,
                                        uint32_t n, int32_t preset, uint32_t *d_out_len, uint32_t *d_crc, int32_t *d_status,
                                        void *stream) {
     if (n == 0) return 0;
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
+    Launch L;
+    int32_t rc = L.begin(stream, false); /* (three work counters of its own, in the scratch) */
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
+    DeviceCtx *c = L.c;
+    hipStream_t s = L.s;
     LzmaEncArgs a;
-    a.in = (const uint8_t *)d_in;
-    a.in_off = d_in_off;
-    a.in_len = d_in_len;
-    a.out = (uint8_t *)d_out;
-    a.out_off = d_out_off;
-    a.out_cap = d_out_cap;
+    set_fields(a, c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, nullptr, d_crc, d_status);
     a.mode = d_mode;
-    a.n = n;
     a.maxb = max_in_len ? (max_in_len + MZ_DEF_BLOCK - 1) / MZ_DEF_BLOCK : 1u;
-    a.ways = (preset >= 0 && preset <= 3) ? 1u : MZ_DEF_WAYS_BEST;
-    a.far_depth = MZ_LZE_DEPTH_FOR_PRESET(preset);
-    if (a.ways > 1u && !big_lds_ok(c->big_lds_tok, (const void *)k_lz_tokenize_batch, MZ_WAVES_PER_WG * (sizeof(mz_lz_tok_lds) + MZ_DEF_XHEAD_BYTES)))
-        a.ways = 1u; /* (128 KiB of dynamic LDS per workgroup not granted: the one-candidate class) */
-    a.out_len = d_out_len;
-    a.crc = d_crc;
-    a.status = d_status;
-    a.tabs = c->d_tabs;
+    set_lz_class(c, a, preset);
     /* token scratch: 4 bytes per input position of the largest entry, for every entry; when an entry has more than one
      * block, as much again for the chain pass's links and 1 MiB of table per resident wave of that pass */
     const size_t items = (size_t)n * a.maxb;
     const size_t tok_words = items * MZ_DEF_BLOCK;
-    const uint32_t chain_waves = a.maxb > 1u ? (n < MZ_LZE_CHAIN_WAVES ? n : MZ_LZE_CHAIN_WAVES) : 0u;
+    const uint32_t chain_waves = a.maxb > 1u ? resident_grid(n, MZ_LZE_CHAIN_WAVES) : 0u;
     const size_t link_words = chain_waves ? tok_words + ((size_t)chain_waves << MZ_LZE_FAR_HBITS) : 0u;
-    int slot = -1;
-    void *scratch = nullptr;
-    rc = scratch_acquire(c, (tok_words + link_words) * sizeof(uint32_t) + items * sizeof(uint32_t) + 64, s, &slot, &scratch);
+    ScratchLease sc;
+    rc = sc.get(&c->scratch, (tok_words + link_words) * sizeof(uint32_t) + items * sizeof(uint32_t) + 64, s);
     if (rc) return rc;
-    a.tok = (uint32_t *)scratch;
+    a.tok = (uint32_t *)sc.p;
     a.links = chain_waves ? a.tok + tok_words : nullptr;
     a.chain_head = chain_waves ? a.links + tok_words : nullptr;
     a.skip_blocks = 0;
     a.ntok = a.tok + tok_words + link_words;
     a.counter = a.ntok + items; /* three work counters behind the token counts */
-    {
-        const hipError_t me = hipMemsetAsync(a.counter, 0, 3 * sizeof(uint32_t), s);
-        if (me != hipSuccess) {
-            (void)scratch_release(c, slot, s);
-            return fail("hipMemsetAsync", me);
-        }
-    }
+    HIP_TRY(hipMemsetAsync(a.counter, 0, 3 * sizeof(uint32_t), s));
     launch_lz_parse(c, s, a, chain_waves);
-    {
-        uint32_t resident = (uint32_t)c->cu_count * 9u; /* 17 KiB LDS per single-wave workgroup */
-        hipLaunchKernelGGL(k_lzma_rc_encode_batch, dim3(n < resident ? n : resident), dim3(64), 0, s, a);
-    }
-    const hipError_t le = hipGetLastError();
-    rc = scratch_release(c, slot, s);
-    if (le != hipSuccess) return fail("k_lzma_rc_encode_batch", le);
-    return rc;
+    hipLaunchKernelGGL(k_lzma_rc_encode_batch, dim3(resident_grid(n, (uint32_t)c->cu_count * 9u)), dim3(64), 0, s, a); /* 17 KiB LDS per single-wave workgroup */
+    return launched("k_lzma_rc_encode_batch", hipGetLastError(), sc);
 }
 
 } // extern "C"
@@ -883,7 +641,7 @@ namespace {
 hipError_t launch_find(const DeviceCtx *c, const ParFindArgs &a, hipStream_t s, int which) {
     const uint64_t per_wg = which ? 256u : 256u * 32u;
     const uint64_t want = ((uint64_t)(a.b1 - a.b0) + per_wg - 1u) / per_wg;
-    const uint32_t grid = (uint32_t)(want < (uint64_t)c->cu_count * 32u ? (want ? want : 1u) : (uint64_t)c->cu_count * 32u);
+    const uint32_t grid = resident_grid(want ? want : 1u, (uint64_t)c->cu_count * 32u);
     if (which)
         hipLaunchKernelGGL(k_find_blocks_lane, dim3(grid), dim3(256), 0, s, a);
     else
@@ -900,8 +658,8 @@ hipError_t launch_check(const DeviceCtx *c, const ParFindArgs &f, uint32_t *out,
     a.cap = f.cap;
     a.out = out;
     a.out_count = out_count;
-    const uint32_t want = (f.cap + 255u) / 256u, most = (uint32_t)c->cu_count * 4u; /* (the count is on the device: a grid-stride loop over it) */
-    hipLaunchKernelGGL(k_check_headers, dim3(want < most ? want : most), dim3(256), 0, s, a);
+    /* (the count is on the device: a grid-stride loop over it) */
+    hipLaunchKernelGGL(k_check_headers, dim3(resident_grid((f.cap + 255u) / 256u, (uint32_t)c->cu_count * 4u)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 int header_check_on() { // MZHIP_HEADER_CHECK=0: every candidate of the search goes to the counting pass, as before round 6 (A/B)
@@ -985,22 +743,19 @@ struct DevParBackend {
         a.mode = mode;
         a.res = d_res;
         a.tabs = c->d_tabs;
-        CounterLease lease;
-        int32_t rc = lease.get(c, s);
+        CounterLease head;
+        int32_t rc = head.get(&c->counters, s);
         if (rc) return rc;
-        a.counter = lease.p;
-        const uint32_t need = (n + MZ_WAVES_PER_WG - 1) / MZ_WAVES_PER_WG, resident = (uint32_t)(c->cu_count * wgs_per_cu);
-        const uint32_t grid = need < resident ? (need ? need : 1u) : resident;
-        int slot = -1;
-        void *scratch = nullptr;
-        rc = scratch_acquire(c, (size_t)grid * MZ_WAVES_PER_WG * MZ_REC_BYTES + 1024, s, &slot, &scratch);
+        a.counter = head.p;
+        const uint32_t need = (n + MZ_WAVES_PER_WG - 1) / MZ_WAVES_PER_WG;
+        const uint32_t grid = resident_grid(need ? need : 1u, (uint32_t)(c->cu_count * wgs_per_cu));
+        ScratchLease sc;
+        rc = sc.get(&c->scratch, (size_t)grid * MZ_WAVES_PER_WG * MZ_REC_BYTES + 1024, s);
         if (rc) return rc;
-        a.rec = (uint8_t *)scratch;
+        a.rec = (uint8_t *)sc.p;
         hipLaunchKernelGGL(k_inflate_blocks, dim3(grid), dim3(MZ_WAVES_PER_WG * 64), MZ_CRC_TAB_BYTES + MZ_WAVES_PER_WG * MZ_LDS_STRIDE, s, a);
-        const hipError_t le = hipGetLastError();
-        const int32_t rr = scratch_release(c, slot, s);
-        if (le != hipSuccess) return fail("k_inflate_blocks", le);
-        if (rr) return rr;
+        rc = launched("k_inflate_blocks", hipGetLastError(), sc);
+        if (rc) return rc;
         static_assert(sizeof(MzParBlock) == 16, "four words per candidate, as mz_inflate_one_block writes them");
         HIP_TRY(mz_d2h_on(s, res, d_res, (size_t)n * 16));
         return 0;
@@ -1013,7 +768,7 @@ struct DevParBackend {
         a.total = total;
         a.changed = d_count + 1;
         const uint64_t want = ((uint64_t)(total - hist) + 255u) / 256u;
-        const uint32_t grid = (uint32_t)(want < (uint64_t)c->cu_count * 32u ? (want ? want : 1u) : (uint64_t)c->cu_count * 32u);
+        const uint32_t grid = resident_grid(want ? want : 1u, (uint64_t)c->cu_count * 32u);
         for (uint32_t r = 0; r < 40u; r++) { /* (2^40 > any chain inside a 2 GiB window) */
             HIP_TRY(hipMemsetAsync(d_count + 1, 0, 4, s));
             /* two rounds (of up to four links each) per look at the flag: the look is a round trip to the host */
@@ -1100,6 +855,13 @@ struct DevLargeBackend {
         return 0;
     }
 };
+static int par_trace() { // MZHIP_PAR_TRACE=1: what every window and large entry cost, step by step, on stderr
+    static const int on = [] {
+        const char *e = getenv("MZHIP_PAR_TRACE");
+        return (e && e[0] == '1') ? 1 : 0;
+    }();
+    return on;
+}
 static int par_wgs_per_cu() { /* resident workgroups per CU of k_inflate_blocks (asked once) */
     static std::atomic<int> s_wgs{0};
     int wgs = s_wgs.load(std::memory_order_relaxed);
@@ -1143,23 +905,19 @@ int32_t mzhip_inflate_large(const void *d_in, uint32_t in_len, void *d_out, uint
     be.o_count = be.o_res + arr * 4;
     be.o_meta = be.o_count + 256;
     const size_t o_ck = be.o_meta + 256, total = o_ck + ck_max * 16;
-    int slot = -1;
-    void *scratch = nullptr;
-    rc = scratch_acquire(c, total, s, &slot, &scratch);
+    ScratchLease sc;
+    rc = sc.get(&c->scratch, total, s);
     if (rc) return rc;
-    be.scratch = (uint8_t *)scratch;
+    be.scratch = (uint8_t *)sc.p;
     MzLargeResult r;
     rc = mz_large_entry(be, in_len, out_cap, &r);
     uint32_t k = 0;
     if (!rc && crc && r.out_len) rc = window_checksums(be.d_out, 0, 0, r.out_len, &k, nullptr, be.scratch + o_ck, ck_max, s);
-    static const int trace = [] {
-        const char *e = getenv("MZHIP_PAR_TRACE");
-        return (e && e[0] == '1') ? 1 : 0;
-    }();
+    const int trace = par_trace();
     if (trace)
         fprintf(stderr, "mzhip large entry: %u B in, %u B out, status %d; %u many-wave windows (%u blocks, %.2f ms), %u serial calls (%.2f ms)\n", in_len,
                 r.out_len, r.status, r.par_windows, r.par_blocks, be.t_par * 1e3, r.serial_calls, be.t_serial * 1e3);
-    const int32_t rr = scratch_release(c, slot, s);
+    const int32_t rr = sc.release();
     if (rc) return rc;
     if (rr) return rr;
     if (out_len) *out_len = r.out_len;
@@ -1263,10 +1021,7 @@ int32_t mzhip_inflate_parallel_host(const uint8_t *in, uint32_t in_len, uint8_t 
     be.d_count = (uint32_t *)(base + o_count);
     be.cap = cap;
     be.wgs_per_cu = wgs;
-    static const int trace = [] {
-        const char *e = getenv("MZHIP_PAR_TRACE");
-        return (e && e[0] == '1') ? 1 : 0;
-    }();
+    const int trace = par_trace();
     const double t0 = DevParBackend::now();
     if (trace) HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
     const double t1 = DevParBackend::now();
@@ -1311,25 +1066,25 @@ int32_t mzhip_inflate_parallel_host(const uint8_t *in, uint32_t in_len, uint8_t 
 uint32_t mzhip_lzma_model_bytes(void) { return (uint32_t)(MZ_LZMA_MODEL_U16 * sizeof(uint16_t)); }
 uint32_t mzhip_lzma_encode_history_bytes(void) { return MZ_LZE_FAR_DICT; }
 
-// One window of one ZIP method-14 payload (include/mzhip.h).  buf[0 .. state_in->out_pos) is the dictionary so far.
-int32_t mzhip_lzma_resume_host(const uint8_t *in, uint32_t in_len, uint8_t *buf, uint32_t buf_cap, const mzhip_lzma_state *state_in,
-                               mzhip_lzma_state *state_out, void *model, uint32_t *out_len, uint32_t *in_used) {
-    static_assert(sizeof(mzhip_lzma_state) == sizeof(mz_lzma_state), "mzhip.h and lzma_core.h describe the same sixteen words");
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    if (!model || !state_in) return -102; /* MZ_PARAM_ERROR */
+} // extern "C"
+
+// One window of one stream through the resumable LZMA decoders, k_lzma_resume (ZIP method 14) and k_lzma2_run (an .xz block's
+// chunk sequence): meta block, model, input and [dictionary so far | room for the window] in one staging buffer, one wave.
+template <class State, class Args, class PubState>
+static int32_t lzma_window_host(DeviceCtx *c, const Kernel<Args> &k, const uint8_t *in, uint32_t in_len, uint8_t *buf, uint32_t buf_cap,
+                                const PubState *state_in, PubState *state_out, void *model, uint32_t *out_len, uint32_t *in_used) {
+    static_assert(sizeof(PubState) == sizeof(State), "mzhip.h and the core header describe the same words");
     const uint32_t hist = state_in->out_pos;
     if (hist > buf_cap) return -102;
     const size_t model_bytes = (MZ_LZMA_MODEL_U16 * sizeof(uint16_t) + 15) & ~(size_t)15;
     const size_t in_pad = ((size_t)in_len + 15 + 16) & ~(size_t)15;
     const size_t total = 256 + model_bytes + in_pad + (size_t)buf_cap + 16;
     Staging sc;
-    rc = sc.get(c, total);
+    const int32_t rc = sc.get(c, total);
     if (rc) return rc;
     uint8_t *base = (uint8_t *)sc.p;
     struct Meta {
-        mz_lzma_state rs, st;
+        State rs, st;
         uint32_t out_len, in_used;
         int32_t status;
     } m;
@@ -1342,11 +1097,12 @@ int32_t mzhip_lzma_resume_host(const uint8_t *in, uint32_t in_len, uint8_t *buf,
     if (in_len) HIP_TRY(mz_h2d(d_in, in, in_len));
     if (hist) HIP_TRY(mz_h2d(d_buf, buf, hist));
     Meta *dm = (Meta *)base;
-    LzmaResumeArgs a{d_in, in_len, d_buf, buf_cap, &dm->rs, state_out ? &dm->st : nullptr, (uint16_t *)d_model,
-                     &dm->out_len, &dm->in_used, &dm->status, c->d_tabs};
-    hipLaunchKernelGGL(k_lzma_resume, dim3(1), dim3(64), 0, MZ_HOST_STREAM, a);
+    Args a{d_in, in_len, d_buf, buf_cap, &dm->rs, state_out ? &dm->st : nullptr, (uint16_t *)d_model,
+           &dm->out_len, &dm->in_used, &dm->status, c->d_tabs};
+    set_tab64(a, c->d_tab64, 0);
+    hipLaunchKernelGGL(k.fn, dim3(1), dim3(64), 0, MZ_HOST_STREAM, a);
     const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail("k_lzma_resume", le);
+    if (le != hipSuccess) return fail(k.name, le);
     HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
     HIP_TRY(mz_d2h(&m, base, sizeof(m)));
     if (m.out_len > hist && m.out_len <= buf_cap) HIP_TRY(mz_d2h(buf + hist, d_buf + hist, m.out_len - hist));
@@ -1359,9 +1115,21 @@ int32_t mzhip_lzma_resume_host(const uint8_t *in, uint32_t in_len, uint8_t *buf,
     return m.status;
 }
 
+extern "C" {
+
+// One window of one ZIP method-14 payload (include/mzhip.h).  buf[0 .. state_in->out_pos) is the dictionary so far.
+int32_t mzhip_lzma_resume_host(const uint8_t *in, uint32_t in_len, uint8_t *buf, uint32_t buf_cap, const mzhip_lzma_state *state_in,
+                               mzhip_lzma_state *state_out, void *model, uint32_t *out_len, uint32_t *in_used) {
+    DeviceCtx *c = nullptr;
+    int32_t rc = ctx_for_current(&c);
+    if (rc) return rc;
+    if (!model || !state_in) return -102; /* MZ_PARAM_ERROR */
+    return lzma_window_host<mz_lzma_state, LzmaResumeArgs>(c, MZ_KERNEL(k_lzma_resume), in, in_len, buf, buf_cap, state_in, state_out, model,
+                                                           out_len, in_used);
+}
+
 // One window of one .xz block's LZMA2 chunk sequence (include/mzhip.h).  buf[0 .. state_in->out_pos) is the dictionary so far.
 int32_t mzhip_lzma2_run_host(const mzhip_lzma2_run_args *ap) {
-    static_assert(sizeof(mzhip_lzma2_state) == sizeof(mz_lzma2_state), "mzhip.h and xz_core.h describe the same twenty words");
     if (!ap || ap->size < offsetof(mzhip_lzma2_run_args, in_used) + sizeof(void *)) return -102; /* MZ_PARAM_ERROR */
     mzhip_lzma2_run_args g;
     memset(&g, 0, sizeof(g));
@@ -1370,42 +1138,8 @@ int32_t mzhip_lzma2_run_host(const mzhip_lzma2_run_args *ap) {
     int32_t rc = ctx_for_current(&c);
     if (rc) return rc;
     if (!g.model || !g.state_in || !g.state_out || (!g.in && g.in_len) || !g.buf) return -102;
-    const uint32_t hist = g.state_in->out_pos;
-    if (hist > g.buf_cap) return -102;
-    const size_t model_bytes = (MZ_LZMA_MODEL_U16 * sizeof(uint16_t) + 15) & ~(size_t)15;
-    const size_t in_pad = ((size_t)g.in_len + 15 + 16) & ~(size_t)15;
-    const size_t total = 256 + model_bytes + in_pad + (size_t)g.buf_cap + 16;
-    Staging sc;
-    rc = sc.get(c, total);
-    if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
-    struct Meta {
-        mz_lzma2_state rs, st;
-        uint32_t out_len, in_used;
-        int32_t status;
-    } m;
-    static_assert(sizeof(Meta) <= 256, "meta block");
-    memset(&m, 0, sizeof(m));
-    memcpy(&m.rs, g.state_in, sizeof(m.rs));
-    uint8_t *d_model = base + 256, *d_in = d_model + model_bytes, *d_buf = d_in + in_pad;
-    HIP_TRY(mz_h2d(base, &m, sizeof(m)));
-    if (g.state_in->flags & 1u) HIP_TRY(mz_h2d(d_model, g.model, MZ_LZMA_MODEL_U16 * sizeof(uint16_t)));
-    if (g.in_len) HIP_TRY(mz_h2d(d_in, g.in, g.in_len));
-    if (hist) HIP_TRY(mz_h2d(d_buf, g.buf, hist));
-    Meta *dm = (Meta *)base;
-    Lzma2RunArgs a{d_in, g.in_len, d_buf, g.buf_cap, &dm->rs, &dm->st, (uint16_t *)d_model, &dm->out_len, &dm->in_used, &dm->status,
-                   c->d_tabs, c->d_tab64};
-    hipLaunchKernelGGL(k_lzma2_run, dim3(1), dim3(64), 0, MZ_HOST_STREAM, a);
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail("k_lzma2_run", le);
-    HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
-    HIP_TRY(mz_d2h(&m, base, sizeof(m)));
-    if (m.out_len > hist && m.out_len <= g.buf_cap) HIP_TRY(mz_d2h(g.buf + hist, d_buf + hist, m.out_len - hist));
-    memcpy(g.state_out, &m.st, sizeof(m.st));
-    if (m.st.flags & 1u) HIP_TRY(mz_d2h(g.model, d_model, MZ_LZMA_MODEL_U16 * sizeof(uint16_t)));
-    if (g.out_len) *g.out_len = m.out_len;
-    if (g.in_used) *g.in_used = m.in_used;
-    return m.status;
+    return lzma_window_host<mz_lzma2_state, Lzma2RunArgs>(c, MZ_KERNEL(k_lzma2_run), g.in, g.in_len, g.buf, g.buf_cap, g.state_in, g.state_out,
+                                                          g.model, g.out_len, g.in_used);
 }
 
 // One segment of one ZIP method-14 payload (include/mzhip.h): in = [skip_blocks x 64 KiB of the stream's previous bytes |
@@ -1448,33 +1182,8 @@ int32_t mzhip_lzma_encode_resume_host(const uint8_t *in, uint32_t in_len, uint32
     Meta *dm = (Meta *)base;
     hipStream_t s = MZ_HOST_STREAM;
     LzmaEncResumeArgs r;
-    LzmaEncArgs &a = r.a;
-    a.in = base;
-    a.in_off = &dm->in_off;
-    a.in_len = &dm->in_len;
-    a.out = base;
-    a.out_off = &dm->out_off;
-    a.out_cap = &dm->out_cap;
-    a.mode = nullptr;
-    a.n = 1;
-    a.maxb = maxb;
-    a.ways = (preset >= 0 && preset <= 3) ? 1u : MZ_DEF_WAYS_BEST;
-    a.far_depth = MZ_LZE_DEPTH_FOR_PRESET(preset);
-    if (a.ways > 1u && !big_lds_ok(c->big_lds_tok, (const void *)k_lz_tokenize_batch, MZ_WAVES_PER_WG * (sizeof(mz_lz_tok_lds) + MZ_DEF_XHEAD_BYTES)))
-        a.ways = 1u;
-    a.out_len = &dm->out_len;
-    a.crc = &dm->crc;
-    a.status = &dm->status;
-    a.tabs = c->d_tabs;
-    a.tok = (uint32_t *)(d_out + ((cap + 63u) & ~63u));
-    a.links = a.tok + (size_t)maxb * MZ_DEF_BLOCK;
-    a.chain_head = a.links + (size_t)maxb * MZ_DEF_BLOCK;
-    a.skip_blocks = skip_blocks; /* the history in front of the segment is linked (it is what the segment's links point into), not parsed */
-    a.ntok = a.chain_head + ((size_t)1 << MZ_LZE_FAR_HBITS);
-    a.counter = a.ntok + maxb;
-    HIP_TRY(hipMemsetAsync(a.counter, 0, 3 * sizeof(uint32_t), s));
-    if (in_len <= MZ_DEF_BLOCK) a.links = nullptr;
-    launch_lz_parse(c, s, a, 1u);
+    rc = lz_parse_one_stream(c, s, r.a, base, dm, maxb, skip_blocks, preset, (uint32_t *)(d_out + ((cap + 63u) & ~63u)));
+    if (rc) return rc;
     r.skip_blocks = skip_blocks;
     r.rs = &dm->rs;
     r.st = last ? nullptr : &dm->st;
@@ -1549,41 +1258,13 @@ static int32_t xz_encode_impl(const uint8_t *in, uint32_t in_len, int32_t preset
         Meta *dm = (Meta *)base;
         hipStream_t s = MZ_HOST_STREAM;
         LzmaEncChunksArgs r;
-        LzmaEncArgs &a = r.a;
-        a.in = base;
-        a.in_off = &dm->in_off;
-        a.in_len = &dm->in_len;
-        a.out = base;
-        a.out_off = &dm->out_off;
-        a.out_cap = &dm->out_cap;
-        a.mode = nullptr;
-        a.n = 1;
-        a.maxb = np;
-        a.ways = (preset >= 0 && preset <= 3) ? 1u : MZ_DEF_WAYS_BEST;
-        a.far_depth = MZ_LZE_DEPTH_FOR_PRESET(preset);
-        if (a.ways > 1u && !big_lds_ok(c->big_lds_tok, (const void *)k_lz_tokenize_batch, MZ_WAVES_PER_WG * (sizeof(mz_lz_tok_lds) + MZ_DEF_XHEAD_BYTES)))
-            a.ways = 1u;
-        a.out_len = &dm->out_len;
-        a.crc = &dm->crc;
-        a.status = &dm->status;
-        a.tabs = c->d_tabs;
-        a.tok = (uint32_t *)(d_out + ((out_bytes + 63) & ~(size_t)63));
-        a.links = a.tok + tok_words;
-        a.chain_head = a.links + tok_words;
-        a.skip_blocks = 0;
-        a.ntok = a.chain_head + ((size_t)1 << MZ_LZE_FAR_HBITS);
-        a.counter = a.ntok + np;
-        HIP_TRY(hipMemsetAsync(a.counter, 0, 3 * sizeof(uint32_t), s));
-        if (np <= 1u) a.links = nullptr;
-        launch_lz_parse(c, s, a, 1u);
+        rc = lz_parse_one_stream(c, s, r.a, base, dm, np, 0, preset, (uint32_t *)(d_out + ((out_bytes + 63) & ~(size_t)63)));
+        if (rc) return rc;
         r.nchunks = np;
         r.chunk_cap = pcap;
         r.chunk_len = (uint32_t *)(base + meta_pad);
         r.chunk_status = (int32_t *)(r.chunk_len + np);
-        {
-            const uint32_t resident = (uint32_t)c->cu_count * 9u; /* 17 KiB LDS per single-wave workgroup */
-            hipLaunchKernelGGL(k_lzma2_chunks_encode, dim3(np < resident ? np : resident), dim3(64), 0, s, r);
-        }
+        hipLaunchKernelGGL(k_lzma2_chunks_encode, dim3(resident_grid(np, (uint32_t)c->cu_count * 9u)), dim3(64), 0, s, r); /* 17 KiB LDS per single-wave workgroup */
         {
             const hipError_t le = hipGetLastError();
             if (le != hipSuccess) return fail("k_lzma2_chunks_encode", le);
@@ -1774,7 +1455,7 @@ static int32_t deflate_segment_host(const uint8_t *in, uint32_t in_len, uint32_t
             pa.dst_off = d_in_off; /* (the pieces' input offsets are done with as well) */
             pa.n = np;
             if (mz_h2d(d_in_off, dst.data(), (size_t)np * 8) == hipSuccess) {
-                hipLaunchKernelGGL(k_pack_pieces, dim3(np < 1024u ? np : 1024u), dim3(256), 0, MZ_HOST_STREAM, pa);
+                hipLaunchKernelGGL(k_pack_pieces, dim3(resident_grid(np, 1024u)), dim3(256), 0, MZ_HOST_STREAM, pa);
                 if (hipGetLastError() == hipSuccess && (sum == 0 || mz_d2h(out, base + meta_pad, (size_t)sum) == hipSuccess)) packed = true;
                 else rc = -104;
             } else

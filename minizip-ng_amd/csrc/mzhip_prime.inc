@@ -311,7 +311,7 @@ struct PrimeLaneSet {
 };
 std::mutex g_lane_mu;
 // Parked lane sets, per device.  A set that has been made is NEVER destroyed: the scratch and work-queue caches of the runtime
-// keep events that were recorded on a lane's stream (scratch_release, CounterLease) and ask them later, and this HIP runtime
+// keep events that were recorded on a lane's stream (the leases of mzhip_slots.inc) and ask them later, and this HIP runtime
 // looks at the stream an event was last recorded on -- after hipStreamDestroy that is freed memory, and the answer was
 // "operation not permitted when stream is capturing" for some later launch of some other thread (found in round 6, when the
 // windows of a rolled archive made two primes at once -- and with it a second, short-lived set -- the normal case).  As many

@@ -1,7 +1,8 @@
 // mzhip_runtime.h -- the seam between the two halves of libmzhip.so's C++ runtime.  PRIVATE: not part of the ABI, every
 // name here has hidden visibility.
 //   device TU  mzhip_kernels.hip + mzhip_launch.inc (hipcc): the kernels and every function whose body names a kernel, a
-//              kernel argument struct or a constant of a core header -- device context, scratch and work-queue caches, launchers;
+//              kernel argument struct or a constant of a core header -- device context, launchers -- and the one definition of
+//              the scratch and work-queue caches (mzhip_slots.inc, whose declarations both halves see: the leases below);
 //   host TUs   mzhip_host.cpp, mzhip_crc_host.cpp, mzhip_prime.cpp (the host C++ compiler, <hip/hip_runtime_api.h> only):
 //              device queries, the per-thread stream pool, staging, the one-entry host calls that only call launchers, the
 //              CRC lane, the RCCL gather, both prime caches.
@@ -15,6 +16,8 @@
 #include <stdint.h>
 
 #include "../../include/mzhip.h"
+
+#include "mzhip_slots.inc"
 
 namespace mzh {
 
@@ -36,8 +39,8 @@ struct DeviceCtx; // per-device state of the launchers: opaque on the host side
 constexpr int kMaxDevices = 16;
 int32_t ctx_for_current(DeviceCtx **out);
 int ctx_device(const DeviceCtx *c); // the device index `c` belongs to
-int32_t scratch_acquire(DeviceCtx *c, size_t bytes, hipStream_t s, int *slot, void **p);
-int32_t scratch_release(DeviceCtx *c, int slot, hipStream_t s);
+struct ScratchCache;
+ScratchCache *ctx_scratch(DeviceCtx *c); // the device's cache of scratch buffers: what a ScratchLease (mzhip_slots.inc) is taken from
 // mzhip_deflate_batch_level with `d_warm`: bytes in front of each piece that are hashed as history, not coded (or null)
 int32_t deflate_batch_launch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_warm, void *d_out,
                              const uint64_t *d_out_off, const uint32_t *d_out_cap, const uint8_t *d_final, uint32_t n, int32_t level,
@@ -76,17 +79,8 @@ static inline hipError_t mz_d2h(void *dst, const void *src, size_t n) {
 }
 // Staging of the synchronous host-buffer calls: a buffer of the scratch cache instead of a hipMalloc / hipFree pair
 // per call (hipFree alone is a device-wide synchronisation); released when the call returns, after its own sync.
-struct Staging {
-    DeviceCtx *c = nullptr;
-    int slot = -1;
-    void *p = nullptr;
-    int32_t get(DeviceCtx *ctx, size_t bytes) {
-        c = ctx;
-        return scratch_acquire(ctx, bytes, MZ_HOST_STREAM, &slot, &p);
-    }
-    ~Staging() {
-        if (slot >= 0) (void)scratch_release(c, slot, MZ_HOST_STREAM);
-    }
+struct Staging : ScratchLease {
+    int32_t get(DeviceCtx *ctx, size_t bytes) { return ScratchLease::get(ctx_scratch(ctx), bytes, MZ_HOST_STREAM); }
 };
 
 // ---- defined in mzhip_host.cpp: checksums of the new bytes of a decoded window (the many-wave decoders of the device TU ask them too)

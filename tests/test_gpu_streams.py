@@ -1,7 +1,8 @@
 """Concurrent use of the batch ABI: several host threads, each on its own HIP stream, running the two encoders that
-need per-launch device scratch (K4 tokens, K6 tokens) back to back without synchronising in between.  The scratch
-cache (scratch_acquire in mzhip_launch.inc) must never hand two in-flight launches on different streams the same
-buffer; every result is checked by inflating / LZMA-decoding it on the CPU."""
+need per-launch device scratch (K4 tokens, K6 tokens) back to back without synchronising in between, and one thread on
+more streams than the caches have slots.  The scratch cache and the cache of work-queue heads (ScratchLease / CounterLease,
+mzhip_slots.inc) must never hand two in-flight launches on different streams the same buffer or head; every result is
+checked on the CPU."""
 import ctypes as C
 import lzma
 import threading
@@ -89,6 +90,43 @@ def test_encoders_on_concurrent_streams(gpu):
                     assert lzma.decompress(z[4:9] + b"\xff" * 8 + z[9:], format=lzma.FORMAT_ALONE) == datas[i], (t, kind, i)
                 checked += 1
     assert checked > 300
+
+
+def test_decoders_on_many_streams(gpu):
+    """One thread, 40 streams -- more than the 32 scratch slots, and the 64 work-queue heads wrap --, two rounds per stream
+    without synchronising: mzhip_inflate_batch over 8 raw-DEFLATE entries of 4 KiB of text (another seed per stream and
+    round: a record buffer or a head shared by two launches in flight cannot go unnoticed), then mzhip_crc32_batch over its
+    outputs on the same stream.  After ONE synchronise every status is 0, every output the input, both CRCs zlib's."""
+    import torch
+
+    L = gpu.mz.lib()
+    dev = torch.device("cuda", 0)
+    n_streams, rounds, n, size = 40, 2, 8, 4096
+    streams = [torch.cuda.Stream(device=dev) for _ in range(n_streams)]
+    jobs = []
+    for r in range(rounds):
+        for k, stream in enumerate(streams):
+            datas = synth.slices(n, size, 700 + 2 * k + r)
+            b = gpu.make_batch([synth.deflate_raw(d, 6) for d in datas], [size] * n)
+            out_len, in_used, crc, status, crc2 = (torch.full((n,), -1, dtype=torch.int32, device=dev) for _ in range(5))
+            jobs.append((stream, datas, b, out_len, in_used, crc, status, crc2))
+    torch.cuda.synchronize()                                                # (the uploads above: torch's own stream)
+    for stream, datas, b, out_len, in_used, crc, status, crc2 in jobs:      # no synchronisation between the launches
+        rc = L.mzhip_inflate_batch(b["d_in"].data_ptr(), b["in_off"].data_ptr(), b["in_len"].data_ptr(), b["d_out"].data_ptr(),
+                                   b["out_off"].data_ptr(), b["out_cap"].data_ptr(), n, out_len.data_ptr(), in_used.data_ptr(),
+                                   crc.data_ptr(), status.data_ptr(), stream.cuda_stream)
+        assert rc == 0, (rc, L.mzhip_last_error())
+        rc = L.mzhip_crc32_batch(b["d_out"].data_ptr(), b["out_off"].data_ptr(), out_len.data_ptr(), n, None, crc2.data_ptr(),
+                                 stream.cuda_stream)
+        assert rc == 0, (rc, L.mzhip_last_error())
+    torch.cuda.synchronize()
+    for j, (stream, datas, b, out_len, in_used, crc, status, crc2) in enumerate(jobs):
+        h = b["d_out"].cpu().numpy()
+        ol, st, k1, k2 = out_len.cpu().numpy(), status.cpu().numpy(), gpu.mz.u32(crc), gpu.mz.u32(crc2)
+        assert (st == 0).all(), (j, st)
+        for i, d in enumerate(datas):
+            assert int(ol[i]) == len(d) and gpu.entry_bytes(b, h, i, int(ol[i])) == d, (j, i)
+            assert k1[i] == zlib.crc32(d) and k2[i] == zlib.crc32(d), (j, i)
 
 
 def test_one_window_on_many_waves(gpu):

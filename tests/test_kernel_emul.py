@@ -1027,6 +1027,18 @@ def test_parallel_window_candidate_order(tmp_path):
     assert r.returncode == 0 and "0 of 300 differ" in r.stdout, r.stdout + r.stderr
 
 
+def test_slot_cache_rules(tmp_path):
+    """The scratch and work-queue caches behind every launch (minizip-ng_amd/csrc/mzhip_slots.inc) over a stand-in for the
+    runtime API in which the test decides when an event has completed: tests/unit_slot_cache.cpp checks the same-stream
+    shortcut, the event guard across streams and across threads on hipStreamPerThread, best fit, the replacement of an idle
+    buffer that is too small, that a held slot is nobody else's (-104 with every slot held), that the wait for a busy slot
+    happens outside the lock, that a lease dropped by an early return gives its slot back, and the heads' round robin."""
+    exe = str(tmp_path / "unit_slot_cache")
+    subprocess.run(["g++", "-O2", "-pthread", os.path.join(ROOT, "tests", "unit_slot_cache.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "slot cache: 0 of " in r.stdout, r.stdout + r.stderr
+
+
 def test_deflate_pieces_with_history(emu):
     """K4 cuts ONE stream into pieces of 16 KiB for as many waves (the WRITE shim's segments, mzhip_prime_write's entries); every
     piece but the first is handed the 32 KiB in front of it (`warm`): they are hashed into the buckets before its first position
