@@ -9,7 +9,9 @@
  * zlib-ng already differ): parity for this kernel is "the reference's inflate of these bytes returns the input,
  * and the CRC matches" (hard parts).
  *
- * MI355X mapping, pass 1 (tokens), 64 input positions per step, one per lane:
+ * MI355X mapping, pass 1 (tokens), 64 input positions per step, one per lane.  The step's vocabulary -- hash, buckets,
+ * inheritance, lazy rule, selection -- is shared with the LZMA tokenizer and lives in lz77_core.h / lz77_select.inc; what
+ * is written here is how a bucket's candidates are measured and what becomes of the tokens:
  *   - match finding: each lane hashes its 4 bytes, looks the hash up in a per-wave LDS table of recent
  *     positions (read-then-update) and measures the match in place with dword compares (min 4, max 258, 32 KiB);
  *   - greedy token selection is the same successor-chain problem as in the decoder (f(l) = l + len(l) or
@@ -27,6 +29,7 @@
 #define MZHIP_DEFLATE_CORE_H
 
 #include "crc32_core.h"
+#include "lz77_core.h"
 #include "wave.h"
 
 /* MZ_PROF (measurement builds): cycles per section of K4 go to mz_prof_buf[16..] (see inflate_core.h) */
@@ -57,10 +60,6 @@
 #else
 #define MZ_DPRIO_AT(i) ((void)0)
 #endif
-#ifndef MZ_DEF_HBITS
-#define MZ_DEF_HBITS 12
-#endif
-#define MZ_DEF_MINMATCH 4u
 #define MZ_DEF_MAXMATCH 258u
 #define MZ_DEF_BLOCK 65536u /* input positions per DEFLATE block = token scratch entries per wave */
 #define MZ_DEF_NLIT 286u
@@ -332,7 +331,7 @@ MZ_DEV void mz_huff_build(mz_deflate_lds *L, uint32_t base, uint32_t n, uint32_t
  * wave-uniform. */
 /* ways / xhead: the match finder keeps the `ways` most recent positions of every hash bucket (1 = the fast class: zlib
  * levels 1-3; MZ_DEF_WAYS_BEST = the default class: levels 4-9 and -1, mz_strm_zlib.c:87,339-343).  Way 0 is L->u.head;
- * ways 1.. are xhead[(w - 1) << MZ_DEF_HBITS | hash], extra LDS behind the wave's mz_deflate_lds (may be NULL for 1).
+ * ways 1.. are xhead, extra LDS behind the wave's mz_deflate_lds (may be NULL for 1): the buckets of lz77_core.h.
  * max_dist: the largest distance a match may use = window - 262 (zlib's MAX_DIST; 32 506 for the 32 KiB window).
  * parse (needs ways > 1): 0 = the lazy rule decides inside every step of 64 positions (levels 4-6 and the default);
  * 1 = COST PARSE (levels 7-9): pass 1 only records every position's best match and counts the lazy choice; the code lengths of that
@@ -341,7 +340,6 @@ MZ_DEV void mz_huff_build(mz_deflate_lds *L, uint32_t base, uint32_t n, uint32_t
  * distance) -- whose choices are then picked up front to back and counted again for the real codes.  What zlib's lazy
  * matching cannot do (shorten a match so that a better one can start, price a far distance against three literals)
  * is worth 3.3 % of the output on the bench corpus with the same match finder (tests/study/enc_parse.c). */
-#define MZ_DEF_WAYS_BEST 4u
 template <uint32_t parse> /* (a template argument: the cost parse needs 160 registers, the other classes run four waves per SIMD on 128) */
 MZ_DEV void mz_deflate_piece(const uint8_t *in, uint32_t in_len, uint32_t warm, uint8_t *out, uint32_t out_cap, uint32_t final,
                              uint32_t *tok, mz_deflate_lds *L, const uint32_t *crc_tab, const mzhip_crc_tables *tabs,
@@ -364,8 +362,7 @@ MZ_DEV void mz_deflate_piece(const uint8_t *in, uint32_t in_len, uint32_t warm, 
         const uint32_t bfinal = (final && blk_end == in_len) ? 1u : 0u;
         /* ================= pass 1: tokens and histograms ================= */
         MZ_LANES {
-            for (uint32_t i = (uint32_t)lane; i < (1u << MZ_DEF_HBITS) / 2u; i += 64u) ((uint32_t *)L->u.head)[i] = 0u;
-            for (uint32_t i = (uint32_t)lane; i < (ways - 1u) * ((1u << MZ_DEF_HBITS) / 2u); i += 64u) ((uint32_t *)xhead)[i] = 0u;
+            MZ_LZ_CLEAR(L->u.head, xhead, ways)
             for (uint32_t i = (uint32_t)lane; i <= MZ_DEF_NSYM; i += 64u) L->freq[i] = 0u;
         }
         MZ_WAVE_SYNC();
@@ -375,7 +372,7 @@ MZ_DEV void mz_deflate_piece(const uint8_t *in, uint32_t in_len, uint32_t warm, 
             for (uint32_t p = 0; ways == 1u && p < warm; p += 64u) { /* one way: the bucket is the newest position, nothing moves down */
                 MZ_LANES {
                     const uint32_t pos = p + (uint32_t)lane;
-                    L->u.head[(mz_load_u32(in + pos) * 2654435761u) >> (32 - MZ_DEF_HBITS)] = (uint16_t)pos;
+                    L->u.head[MZ_LZ_HASH4(mz_load_u32(in + pos))] = (uint16_t)pos;
                 }
             }
             if (ways == 1u) MZ_WAVE_SYNC();
@@ -385,16 +382,11 @@ MZ_DEV void mz_deflate_piece(const uint8_t *in, uint32_t in_len, uint32_t warm, 
                 PV2(uint32_t, wcx, MZ_DEF_WAYS_BEST - 1u);
                 MZ_LANES {
                     const uint32_t pos = p + (uint32_t)lane;
-                    P(wh) = (mz_load_u32(in + pos) * 2654435761u) >> (32 - MZ_DEF_HBITS); /* (pos + 4 <= warm + 3 < in_len or the piece is empty: below) */
-                    P(wc) = (uint32_t)L->u.head[P(wh)];
-                    for (uint32_t w = 1; w < MZ_DEF_WAYS_BEST; w++) P(wcx)[w - 1u] = (w < ways) ? (uint32_t)xhead[((w - 1u) << MZ_DEF_HBITS) | P(wh)] : 0u;
+                    P(wh) = MZ_LZ_HASH4(mz_load_u32(in + pos)); /* (pos + 4 <= warm + 3 < in_len or the piece is empty: below) */
+                    MZ_LZ_BUCKET_READ(L->u.head, xhead, ways, P(wh), 1, 1, wc, wcx)
                 }
                 MZ_WAVE_SYNC();
-                MZ_LANES {
-                    for (uint32_t w = MZ_DEF_WAYS_BEST - 1u; w >= 1u; w--)
-                        if (w < ways) xhead[((w - 1u) << MZ_DEF_HBITS) | P(wh)] = (uint16_t)(w == 1u ? P(wc) : P(wcx)[w - 2u]);
-                    L->u.head[P(wh)] = (uint16_t)(p + (uint32_t)lane);
-                }
+                MZ_LANES { MZ_LZ_BUCKET_PUSH(L->u.head, xhead, ways, P(wh), p + (uint32_t)lane, wc, wcx) }
                 MZ_WAVE_SYNC();
             }
         }
@@ -423,12 +415,10 @@ MZ_DEV void mz_deflate_piece(const uint8_t *in, uint32_t in_len, uint32_t warm, 
             const uint32_t have4 = (pos + 4u <= blk_end) ? 1u : 0u;                                                    \
             const uint32_t v = P(vnx);                                                                                 \
             P(vnx) = (pos + 68u <= blk_end) ? mz_load_u32(in + pos + 64u) : 0u;                                        \
-            const uint32_t h = (v * 2654435761u) >> (32 - MZ_DEF_HBITS);                                               \
+            const uint32_t h = MZ_LZ_HASH4(v);                                                                         \
             P(own_n) = v;                                                                                              \
             P(hh_n) = have4 ? h : 0xFFFFFFFFu;                                                                         \
-            P(cand_n) = have4 ? (uint32_t)L->u.head[h] : 0u;                                                           \
-            for (uint32_t w = 1; w < MZ_DEF_WAYS_BEST; w++)                                                            \
-                P(candx_n)[w - 1u] = (have4 && w < ways) ? (uint32_t)xhead[((w - 1u) << MZ_DEF_HBITS) | h] : 0u;       \
+            MZ_LZ_BUCKET_READ(L->u.head, xhead, ways, h, have4, have4, cand_n, candx_n)                                \
             const uint32_t d = (pos - P(cand_n)) & 0xFFFFu;                                                            \
             uint32_t ok = (have4 && pos + 16u <= blk_end && d >= 1u && d <= max_dist && d <= pos - lo) ? 1u : 0u;      \
             P(pre_n) = ok;                                                                                             \
@@ -461,11 +451,7 @@ MZ_DEV void mz_deflate_piece(const uint8_t *in, uint32_t in_len, uint32_t warm, 
                     P(pb)[k] = P(pb_n)[k];
                 }
                 if (P(hh) != 0xFFFFFFFFu) {
-                    /* the bucket shifts by one: lanes that share a bucket write the same older entries, one of them
-                     * wins way 0 */
-                    for (uint32_t w = MZ_DEF_WAYS_BEST - 1u; w >= 1u; w--)
-                        if (w < ways) xhead[((w - 1u) << MZ_DEF_HBITS) | P(hh)] = (uint16_t)(w == 1u ? P(cand) : P(candx)[w - 2u]);
-                    L->u.head[P(hh)] = (uint16_t)(p + (uint32_t)lane);
+                    MZ_LZ_BUCKET_PUSH(L->u.head, xhead, ways, P(hh), p + (uint32_t)lane, cand, candx)
                 }
             }
             MZ_WAVE_SYNC();
@@ -510,41 +496,14 @@ MZ_DEV void mz_deflate_piece(const uint8_t *in, uint32_t in_len, uint32_t warm, 
                 P(pk) = mlen | ((mlen ? dist : 0u) << 9);
                 P(lit) = (P(hh) != 0xFFFFFFFFu) ? (P(own) & 0xFFu) : (uint32_t)in[pos < blk_end ? pos : blk];
             }
-            if (ways > 1u) {
-                /* a match of length L at position q is a match of length L - k at q + k, same distance: a position whose own
-                 * bucket had lost that candidate inherits it from the lanes 1 and 2 (then up to 3) below -- worth 1.2 % of
-                 * the output under the lazy rule (tests/study/enc_parse.c INH=3) */
-                for (uint32_t sh = 1u; sh <= 2u; sh <<= 1) {
-                    PV(uint32_t, pin);
-                    MZ_GATHER4(pin, pk, 4u * (((uint32_t)lane - sh) & 63u));
-                    MZ_LANES {
-                        const uint32_t il = P(pin) & 511u;
-                        if ((uint32_t)lane >= sh && (uint32_t)lane < nv && il >= MZ_DEF_MINMATCH + sh && il - sh > (P(pk) & 511u))
-                            P(pk) = (il - sh) | (P(pin) & ~511u);
-                    }
-                }
-            }
+            MZ_LZ_INHERIT(pk, nv, ways)
             if (parse) {
                 MZ_LANES {
                     if ((uint32_t)lane < nv) tok[(p - blk) + (uint32_t)lane] = P(pk); /* the cost parse looks at every position's match */
                 }
             }
             MZ_DPROF_MARK(18); /* match measurement */
-            /* lazy evaluation (what zlib does from level 4 up): a match yields to a longer one starting at the
-             * next position -- this position then goes out as a literal */
-            PV(uint32_t, pkn);
-            PV(uint32_t, pkn2);
-            MZ_GATHER4(pkn, pk, 4u * ((uint32_t)lane + 1u));
-            MZ_GATHER4(pkn2, pk, 4u * ((uint32_t)lane + 2u));
-            MZ_LANES {
-                uint32_t mlen = P(pk) & 511u;
-                if (mlen && (uint32_t)lane + 1u < nv && (P(pkn) & 511u) > mlen) mlen = 0u;
-                /* the default class also looks two positions ahead (two literals must buy more than one byte) */
-                if (ways > 1u && mlen && (uint32_t)lane + 2u < nv && (P(pkn2) & 511u) > mlen + 1u) mlen = 0u;
-                P(pk) = mlen ? P(pk) : (P(lit) << 9);
-                const uint32_t nx = (uint32_t)lane + (mlen ? mlen : 1u);
-                P(g1) = ((uint32_t)lane >= nv || nx >= nv) ? (0x1000u | (4u * nx)) : (4u * nx);
-            }
+            MZ_LZ_LAZY(pk, lit, g1, nv, ways)
 #define MZ_DEF_STORE_TOKENS (!parse)
 #include "deflate_select.inc"
 #undef MZ_DEF_STORE_TOKENS
@@ -728,8 +687,7 @@ MZ_DEV void mz_deflate_piece(const uint8_t *in, uint32_t in_len, uint32_t warm, 
                     if ((uint32_t)lane < nv) t = tok[(p - blk) + (uint32_t)lane];
                     const uint32_t mlen = t & 511u;
                     P(pk) = mlen ? t : ((uint32_t)in[(uint32_t)lane < nv ? p + (uint32_t)lane : blk] << 9);
-                    const uint32_t nx = (uint32_t)lane + (mlen ? mlen : 1u);
-                    P(g1) = ((uint32_t)lane >= nv || nx >= nv) ? (0x1000u | (4u * nx)) : (4u * nx);
+                    P(g1) = mz_lz_succ((uint32_t)lane, mlen, nv);
                 }
                 MZ_WAVE_SYNC();
 #define MZ_DEF_STORE_TOKENS 1

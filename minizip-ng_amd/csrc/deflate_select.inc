@@ -1,48 +1,10 @@
-/* deflate_select.inc -- K4, one step of 64 positions: pick the tokens of the chain start, f(start), f(f(start)), ... and
- * count them.  Textually included by mz_deflate_piece() (deflate_core.h) -- in pass 1 behind the lazy rule, and again
- * behind the cost parse -- with P(pk) = every position's token ([8:0] match length or 0, [24:9] distance | literal byte),
- * P(g1) = 4 * successor lane (bit 12: the successor lies beyond the step), nv = valid positions, skip = positions of
- * this step that the previous step's last token covers.  Leaves ntok = tokens of the step (compacted into lanes
- * 0 .. ntok - 1 and, where MZ_DEF_STORE_TOKENS, appended to tok[]), the histograms and xbits updated, skip moved on. */
-            /* greedy selection: lane r <- r-th element of the chain start, f(start), f(f(start)), ... */
-            PV(uint32_t, g2);
-            PV(uint32_t, g4);
-            PV(uint32_t, g8);
-            PV(uint32_t, g16);
-            PV(uint32_t, g32);
-            PV(uint32_t, gt);
-            PV(uint32_t, ct);
-            PV(uint32_t, cpos);
-            MZ_LANES { P(cpos) = (skip >= nv) ? (0x1000u | (4u * skip)) : (4u * skip); }
-#define MZ_DEF_ROUND(gin, gout, bit)                                                         \
-    MZ_GATHER4(gt, gin, P(gin));                                                             \
-    MZ_GATHER4(ct, gin, P(cpos));                                                            \
-    MZ_LANES {                                                                               \
-        P(gout) = (P(gin) & 0x1000u) ? P(gin) : P(gt);                                       \
-        P(cpos) = (((uint32_t)lane & (bit)) && !(P(cpos) & 0x1000u)) ? P(ct) : P(cpos);      \
-    }
-            MZ_DEF_ROUND(g1, g2, 1u)
-            MZ_DEF_ROUND(g2, g4, 2u)
-            MZ_DEF_ROUND(g4, g8, 4u)
-            MZ_DEF_ROUND(g8, g16, 8u)
-            MZ_DEF_ROUND(g16, g32, 16u)
-            MZ_GATHER4(ct, g32, P(cpos));
-            MZ_LANES { P(cpos) = (((uint32_t)lane & 32u) && !(P(cpos) & 0x1000u)) ? P(ct) : P(cpos); }
-#undef MZ_DEF_ROUND
-            uint64_t live;
-            MZ_BALLOT(live, !(P(cpos) & 0x1000u));
-            MZ_DPROF_MARK(19); /* lazy rule + greedy selection */
-            const uint32_t ntok = mz_popc64(live); /* tokens sit in lanes 0..ntok-1 */
-            PV(uint32_t, tpk);
-            MZ_GATHER4(tpk, pk, P(cpos));
-            if (ntok) { /* where the chain left this step: position of the last token + its length */
-                const uint32_t lastpos = MZ_READLANE(cpos, ntok - 1u) >> 2;
-                const uint32_t lastpk = MZ_READLANE(tpk, ntok - 1u);
-                const uint32_t nx = lastpos + ((lastpk & 511u) ? (lastpk & 511u) : 1u);
-                skip = nx > 64u ? nx - 64u : 0u;
-            } else {
-                skip = skip > 64u ? skip - 64u : 0u;
-            }
+/* deflate_select.inc -- K4, one step of 64 positions: the shared selection (lz77_select.inc, which names what it expects
+ * and leaves), then what DEFLATE does with the step's tokens.  Textually included by mz_deflate_piece() (deflate_core.h)
+ * -- in pass 1 behind the lazy rule, and again behind the cost parse.  The tokens are appended to tok[] where
+ * MZ_DEF_STORE_TOKENS; the histograms, xbits and ntokens are updated. */
+#define MZ_LZ_SELECT_MARK MZ_DPROF_MARK(19) /* lazy rule + greedy selection */
+#include "lz77_select.inc"
+#undef MZ_LZ_SELECT_MARK
             MZ_LANES {
                 if ((uint32_t)lane < ntok) {
                     const uint32_t t = P(tpk), mlen = t & 511u;

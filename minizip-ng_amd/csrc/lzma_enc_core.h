@@ -7,8 +7,9 @@
  * length coders, 6-bit distance slots, aligned bits) and doc/zip/appnote.txt:2232-2275 for the ZIP framing.
  *
  * Split along what is parallel and what is not:
- *   mz_lz_tokenize   one wave per 64 KiB block, 64 positions per step: the LZ77 parse of deflate_core.h (hash head
- *                    table in LDS, in-place match measurement, lazy rule, greedy selection by pointer doubling);
+ *   mz_lz_tokenize   one wave per 64 KiB block, 64 positions per step: the LZ77 step of lz77_core.h / lz77_select.inc,
+ *                    which the DEFLATE encoder shares (hash buckets in LDS, inheritance, lazy rule, greedy selection by
+ *                    pointer doubling), around a match measurement of its own (no prefetch, the far links);
  *                    the previous 32 KiB of the stream are hashed first so matches may reach back across the block
  *                    boundary; tokens (literal | length 4..258 + distance <= 32 KiB) go to HBM;
  *   mz_lzma_rc_encode one wave per stream: the adaptive range coder is strictly serial, so the token sequence is
@@ -118,17 +119,14 @@ MZ_DEV void mz_lz_chain(const uint8_t *in, uint32_t in_len, uint32_t *links, uin
 /* LZ77 parse of in[blk, blk_end) (blk_end - blk <= MZ_DEF_BLOCK) of the stream in[0..); matches may start up to 32 KiB
  * before blk -- and, with links (the chain pass's array for the whole stream, or null), wherever those point.  Returns the
  * number of tokens written to tok[]: [8:0] match length (0 = literal), [31:9] distance | literal byte.
- * ways / xhead: as in K4 (deflate_core.h) -- the `ways` most recent positions of every hash bucket are tried and the
+ * ways / xhead: the buckets of lz77_core.h, as in K4 -- the `ways` most recent positions of every hash bucket are tried and the
  * longest match wins; 1 = the fast class (presets 0-3), MZ_DEF_WAYS_BEST = presets 4-9 and the default
  * (mz_strm_lzma.c:81 hands the level to lzma_lzma_preset).  xhead: (ways - 1) more tables behind the wave's LDS.
  * far_depth: links of the chain followed per position (MZ_LZE_DEPTH_FOR_PRESET). */
 MZ_DEV uint32_t mz_lz_tokenize(const uint8_t *in, uint32_t blk, uint32_t blk_end, uint32_t *tok, mz_lz_tok_lds *L,
                                uint32_t ways, uint16_t *xhead, const uint32_t *links, uint32_t far_depth) {
     MZ_LANE_DECL
-    MZ_LANES {
-        for (uint32_t i = (uint32_t)lane; i < (1u << MZ_DEF_HBITS) / 2u; i += 64u) ((uint32_t *)L->head)[i] = 0u;
-        for (uint32_t i = (uint32_t)lane; i < (ways - 1u) * ((1u << MZ_DEF_HBITS) / 2u); i += 64u) ((uint32_t *)xhead)[i] = 0u;
-    }
+    MZ_LANES { MZ_LZ_CLEAR(L->head, xhead, ways) }
     MZ_WAVE_SYNC();
     /* the stream's previous 32 KiB are legal match sources (the dictionary is 64 KiB): enter them into the hash table
      * first, without producing tokens, so that a block does not start with an empty history */
@@ -140,18 +138,14 @@ MZ_DEV uint32_t mz_lz_tokenize(const uint8_t *in, uint32_t blk, uint32_t blk_end
         MZ_LANES {
             const uint32_t pos = p + (uint32_t)lane;
             const uint32_t ok = (pos < blk && pos + 4u <= blk_end) ? 1u : 0u;
-            const uint32_t h = ok ? (mz_load_u32(in + pos) * 2654435761u) >> (32 - MZ_DEF_HBITS) : 0u;
+            const uint32_t h = ok ? MZ_LZ_HASH4(mz_load_u32(in + pos)) : 0u;
             P(hh0) = ok ? h : 0xFFFFFFFFu;
-            P(c0) = (ok && ways > 1u) ? (uint32_t)L->head[h] : 0u;
-            for (uint32_t w = 1; w < MZ_DEF_WAYS_BEST; w++)
-                P(cx0)[w - 1u] = (ok && w < ways) ? (uint32_t)xhead[((w - 1u) << MZ_DEF_HBITS) | h] : 0u;
+            MZ_LZ_BUCKET_READ(L->head, xhead, ways, h, ok && ways > 1u, ok, c0, cx0) /* (one way: nothing moves down, way 0 is not read) */
         }
         MZ_WAVE_SYNC();
         MZ_LANES {
             if (P(hh0) != 0xFFFFFFFFu) {
-                for (uint32_t w = MZ_DEF_WAYS_BEST - 1u; w >= 1u; w--)
-                    if (w < ways) xhead[((w - 1u) << MZ_DEF_HBITS) | P(hh0)] = (uint16_t)(w == 1u ? P(c0) : P(cx0)[w - 2u]);
-                L->head[P(hh0)] = (uint16_t)(p + (uint32_t)lane);
+                MZ_LZ_BUCKET_PUSH(L->head, xhead, ways, P(hh0), p + (uint32_t)lane, c0, cx0)
             }
         }
         MZ_WAVE_SYNC();
@@ -174,18 +168,14 @@ MZ_DEV uint32_t mz_lz_tokenize(const uint8_t *in, uint32_t blk, uint32_t blk_end
             P(fcand) = (links && have4) ? links[pos] : 0u;
             const uint32_t v = P(vnx);
             P(vnx) = (pos + 68u <= blk_end) ? mz_load_u32(in + pos + 64u) : 0u;
-            const uint32_t h = (v * 2654435761u) >> (32 - MZ_DEF_HBITS);
+            const uint32_t h = MZ_LZ_HASH4(v);
             P(hh) = have4 ? h : 0xFFFFFFFFu;
-            P(cand) = have4 ? (uint32_t)L->head[h] : 0u;
-            for (uint32_t w = 1; w < MZ_DEF_WAYS_BEST; w++)
-                P(candx)[w - 1u] = (have4 && w < ways) ? (uint32_t)xhead[((w - 1u) << MZ_DEF_HBITS) | h] : 0u;
+            MZ_LZ_BUCKET_READ(L->head, xhead, ways, h, have4, have4, cand, candx)
         }
         MZ_WAVE_SYNC();
         MZ_LANES {
             if (P(hh) != 0xFFFFFFFFu) {
-                for (uint32_t w = MZ_DEF_WAYS_BEST - 1u; w >= 1u; w--)
-                    if (w < ways) xhead[((w - 1u) << MZ_DEF_HBITS) | P(hh)] = (uint16_t)(w == 1u ? P(cand) : P(candx)[w - 2u]);
-                L->head[P(hh)] = (uint16_t)(p + (uint32_t)lane);
+                MZ_LZ_BUCKET_PUSH(L->head, xhead, ways, P(hh), p + (uint32_t)lane, cand, candx)
             }
         }
         MZ_WAVE_SYNC();
@@ -227,71 +217,11 @@ MZ_DEV uint32_t mz_lz_tokenize(const uint8_t *in, uint32_t blk, uint32_t blk_end
             P(pk) = mlen | ((mlen ? dist : 0u) << 9);
             P(lit) = (uint32_t)in[pos < blk_end ? pos : blk];
         }
-        PV(uint32_t, pkn);
-        PV(uint32_t, pkn2);
-#ifndef MZ_LZE_INHERIT
-#define MZ_LZE_INHERIT 1
-#endif
-        if (MZ_LZE_INHERIT && ways > 1u) {
-            /* a match of length L at position q is a match of length L - k at q + k, same distance: a position whose own
-             * bucket had lost that candidate inherits it from the lanes 1 and 2 below (deflate_core.h does the same) */
-            for (uint32_t sh = 1u; sh <= 2u; sh <<= 1) {
-                PV(uint32_t, pin);
-                MZ_GATHER4(pin, pk, 4u * (((uint32_t)lane - sh) & 63u));
-                MZ_LANES {
-                    const uint32_t il = P(pin) & 511u;
-                    if ((uint32_t)lane >= sh && (uint32_t)lane < nv && il >= MZ_DEF_MINMATCH + sh && il - sh > (P(pk) & 511u))
-                        P(pk) = (il - sh) | (P(pin) & ~511u);
-                }
-            }
-        }
-        MZ_GATHER4(pkn, pk, 4u * ((uint32_t)lane + 1u));
-        MZ_GATHER4(pkn2, pk, 4u * ((uint32_t)lane + 2u));
-        MZ_LANES {
-            uint32_t mlen = P(pk) & 511u;
-            if (mlen && (uint32_t)lane + 1u < nv && (P(pkn) & 511u) > mlen) mlen = 0u; /* lazy rule */
-            if (ways > 1u && mlen && (uint32_t)lane + 2u < nv && (P(pkn2) & 511u) > mlen + 1u) mlen = 0u; /* two ahead */
-            P(pk) = mlen ? P(pk) : (P(lit) << 9);
-            const uint32_t nx = (uint32_t)lane + (mlen ? mlen : 1u);
-            P(g1) = ((uint32_t)lane >= nv || nx >= nv) ? (0x1000u | (4u * nx)) : (4u * nx);
-        }
-        PV(uint32_t, g2);
-        PV(uint32_t, g4);
-        PV(uint32_t, g8);
-        PV(uint32_t, g16);
-        PV(uint32_t, g32);
-        PV(uint32_t, gt);
-        PV(uint32_t, ct);
-        PV(uint32_t, cpos);
-        MZ_LANES { P(cpos) = (skip >= nv) ? (0x1000u | (4u * skip)) : (4u * skip); }
-#define MZ_LZT_ROUND(gin, gout, bit)                                                         \
-    MZ_GATHER4(gt, gin, P(gin));                                                             \
-    MZ_GATHER4(ct, gin, P(cpos));                                                            \
-    MZ_LANES {                                                                               \
-        P(gout) = (P(gin) & 0x1000u) ? P(gin) : P(gt);                                       \
-        P(cpos) = (((uint32_t)lane & (bit)) && !(P(cpos) & 0x1000u)) ? P(ct) : P(cpos);      \
-    }
-        MZ_LZT_ROUND(g1, g2, 1u)
-        MZ_LZT_ROUND(g2, g4, 2u)
-        MZ_LZT_ROUND(g4, g8, 4u)
-        MZ_LZT_ROUND(g8, g16, 8u)
-        MZ_LZT_ROUND(g16, g32, 16u)
-        MZ_GATHER4(ct, g32, P(cpos));
-        MZ_LANES { P(cpos) = (((uint32_t)lane & 32u) && !(P(cpos) & 0x1000u)) ? P(ct) : P(cpos); }
-#undef MZ_LZT_ROUND
-        uint64_t live;
-        MZ_BALLOT(live, !(P(cpos) & 0x1000u));
-        const uint32_t ntok = mz_popc64(live);
-        PV(uint32_t, tpk);
-        MZ_GATHER4(tpk, pk, P(cpos));
-        if (ntok) {
-            const uint32_t lastpos = MZ_READLANE(cpos, ntok - 1u) >> 2;
-            const uint32_t lastpk = MZ_READLANE(tpk, ntok - 1u);
-            const uint32_t nx = lastpos + ((lastpk & 511u) ? (lastpk & 511u) : 1u);
-            skip = nx > 64u ? nx - 64u : 0u;
-        } else {
-            skip = skip > 64u ? skip - 64u : 0u;
-        }
+        MZ_LZ_INHERIT(pk, nv, ways)
+        MZ_LZ_LAZY(pk, lit, g1, nv, ways)
+#define MZ_LZ_SELECT_MARK ((void)0) /* (K6 has no section marks) */
+#include "lz77_select.inc"
+#undef MZ_LZ_SELECT_MARK
         MZ_LANES {
             if ((uint32_t)lane < ntok) tok[ntokens + (uint32_t)lane] = P(tpk);
         }

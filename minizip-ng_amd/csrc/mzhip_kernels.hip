@@ -114,8 +114,8 @@ __global__ __launch_bounds__(MZ_WAVES_PER_WG * 64, MZ_MIN_WAVES_PER_SIMD) void k
         mz_inflate_result r;
         // entry descriptors are wave-uniform: pin them to SGPRs so addresses use the scalar base
         const uint64_t io = a.in_off[e], oo = a.out_off[e];
-        const uint8_t *in = a.in + (((uint64_t)MZ_UNIFORM((uint32_t)(io >> 32)) << 32) | MZ_UNIFORM((uint32_t)io));
-        uint8_t *out = a.out + (((uint64_t)MZ_UNIFORM((uint32_t)(oo >> 32)) << 32) | MZ_UNIFORM((uint32_t)oo));
+        const uint8_t *in = a.in + MZ_UNIFORM64(io);
+        uint8_t *out = a.out + MZ_UNIFORM64(oo);
         mz_inflate_entry(in, MZ_UNIFORM(a.in_len[e]), out, MZ_UNIFORM(a.out_cap[e]), L, crc_tab, a.tabs, 1u, rec,
                          (RESUMABLE && a.resume) ? a.resume + e : nullptr, (RESUMABLE && a.stop) ? a.stop + e : nullptr, &r, nullptr);
         // wave-uniform results: stored by all lanes (same address, same value), see MZ_WAVE_FETCH_ADD
@@ -526,8 +526,8 @@ __global__ __launch_bounds__(MZ_WAVES_PER_WG * 64) void k_wzaes_ctr(WzaesArgs a)
         const uint32_t strength = MZ_UNIFORM((uint32_t)a.strength[e]), sl = mz_wzaes_salt_len(strength);
         const uint32_t n = MZ_UNIFORM(a.in_len[e]) - sl - MZ_WZAES_VERIFY - MZ_WZAES_AUTH;
         const uint64_t io = a.in_off[e], oo = a.out_off[e];
-        const uint8_t *in = a.in + (((uint64_t)MZ_UNIFORM((uint32_t)(io >> 32)) << 32) | MZ_UNIFORM((uint32_t)io));
-        uint8_t *out = a.out + (((uint64_t)MZ_UNIFORM((uint32_t)(oo >> 32)) << 32) | MZ_UNIFORM((uint32_t)oo));
+        const uint8_t *in = a.in + MZ_UNIFORM64(io);
+        uint8_t *out = a.out + MZ_UNIFORM64(oo);
         mz_wzaes_ctr(in + sl + MZ_WZAES_VERIFY, n, out, ek->rk, MZ_UNIFORM(ek->rounds), &tab);
     }
 }
@@ -628,8 +628,8 @@ __global__ __launch_bounds__(MZ_WAVES_PER_WG * 64) void k_wzaes_enc_ctr(WzaesEnc
         const uint32_t strength = MZ_UNIFORM((uint32_t)a.strength[e]), sl = mz_wzaes_salt_len(strength);
         const uint32_t n = MZ_UNIFORM(a.in_len[e]);
         const uint64_t io = a.in_off[e], oo = a.out_off[e];
-        const uint8_t *in = a.in + (((uint64_t)MZ_UNIFORM((uint32_t)(io >> 32)) << 32) | MZ_UNIFORM((uint32_t)io));
-        uint8_t *out = a.out + (((uint64_t)MZ_UNIFORM((uint32_t)(oo >> 32)) << 32) | MZ_UNIFORM((uint32_t)oo));
+        const uint8_t *in = a.in + MZ_UNIFORM64(io);
+        uint8_t *out = a.out + MZ_UNIFORM64(oo);
         mz_wzaes_ctr(in, n, out + sl + MZ_WZAES_VERIFY, ek->rk, MZ_UNIFORM(ek->rounds), &tab);
     }
 }
@@ -687,8 +687,8 @@ __device__ __forceinline__ void deflate_batch_body(const DeflateArgs &a) {
         MZ_WAVE_FETCH_ADD(e, a.counter);
         if (e >= a.n) break;
         const uint64_t io = a.in_off[e], oo = a.out_off[e];
-        const uint8_t *in = a.in + (((uint64_t)MZ_UNIFORM((uint32_t)(io >> 32)) << 32) | MZ_UNIFORM((uint32_t)io));
-        uint8_t *out = a.out + (((uint64_t)MZ_UNIFORM((uint32_t)(oo >> 32)) << 32) | MZ_UNIFORM((uint32_t)oo));
+        const uint8_t *in = a.in + MZ_UNIFORM64(io);
+        uint8_t *out = a.out + MZ_UNIFORM64(oo);
         const uint32_t fin = a.final_flag ? MZ_UNIFORM((uint32_t)a.final_flag[e]) : 1u;
         const uint32_t warm = a.warm ? MZ_UNIFORM(a.warm[e]) : 0u;
         mz_deflate_result r;
@@ -738,7 +738,7 @@ __global__ __launch_bounds__(64) void k_lz_chain_batch(LzmaEncArgs a) {
         const uint32_t len = MZ_UNIFORM(a.in_len[e]);
         if (len <= MZ_DEF_BLOCK || (a.mode && MZ_UNIFORM((uint32_t)a.mode[e]) != 0u)) continue;
         const uint64_t io = a.in_off[e];
-        const uint8_t *in = a.in + (((uint64_t)MZ_UNIFORM((uint32_t)(io >> 32)) << 32) | MZ_UNIFORM((uint32_t)io));
+        const uint8_t *in = a.in + MZ_UNIFORM64(io);
         mz_lz_chain(in, len, a.links + (size_t)e * a.maxb * MZ_DEF_BLOCK, a.chain_head + ((size_t)blockIdx.x << MZ_LZE_FAR_HBITS));
     }
 }
@@ -761,7 +761,7 @@ __global__ __launch_bounds__(MZ_WAVES_PER_WG * 64) void k_lz_tokenize_batch(Lzma
         uint32_t nt = 0;
         if (lo < len && b >= a.skip_blocks) {
             const uint64_t io = a.in_off[e];
-            const uint8_t *in = a.in + (((uint64_t)MZ_UNIFORM((uint32_t)(io >> 32)) << 32) | MZ_UNIFORM((uint32_t)io));
+            const uint8_t *in = a.in + MZ_UNIFORM64(io);
             const uint32_t far = (a.links && len > MZ_DEF_BLOCK && !(a.mode && MZ_UNIFORM((uint32_t)a.mode[e]) != 0u)) ? 1u : 0u;
             nt = mz_lz_tokenize(in, lo, (len - lo < MZ_DEF_BLOCK) ? len : lo + MZ_DEF_BLOCK, a.tok + (size_t)w * MZ_DEF_BLOCK, L,
                                 MZ_UNIFORM(a.ways), xhead, far ? a.links + (size_t)e * a.maxb * MZ_DEF_BLOCK : (const uint32_t *)nullptr,
@@ -783,8 +783,8 @@ __global__ __launch_bounds__(64) void k_lzma_rc_encode_batch(LzmaEncArgs a) {
         MZ_WAVE_FETCH_ADD(e, a.counter + 1);
         if (e >= a.n) break;
         const uint64_t io = a.in_off[e], oo = a.out_off[e];
-        const uint8_t *in = a.in + (((uint64_t)MZ_UNIFORM((uint32_t)(io >> 32)) << 32) | MZ_UNIFORM((uint32_t)io));
-        uint8_t *out = a.out + (((uint64_t)MZ_UNIFORM((uint32_t)(oo >> 32)) << 32) | MZ_UNIFORM((uint32_t)oo));
+        const uint8_t *in = a.in + MZ_UNIFORM64(io);
+        uint8_t *out = a.out + MZ_UNIFORM64(oo);
         mz_lzma_enc_result r;
         mz_lzma_rc_encode(in, MZ_UNIFORM(a.in_len[e]), a.tok + (size_t)e * a.maxb * MZ_DEF_BLOCK, a.ntok + (size_t)e * a.maxb,
                           a.mode ? MZ_UNIFORM((uint32_t)a.mode[e]) : 0u, out, MZ_UNIFORM(a.out_cap[e]), &lds, crc_tab, a.tabs, &r);
@@ -812,8 +812,8 @@ __global__ __launch_bounds__(64) void k_lzma2_chunks_encode(LzmaEncChunksArgs r)
     MZ_LANE_DECL
     const LzmaEncArgs &a = r.a;
     const uint64_t io = a.in_off[0], oo = a.out_off[0];
-    const uint8_t *in = a.in + (((uint64_t)MZ_UNIFORM((uint32_t)(io >> 32)) << 32) | MZ_UNIFORM((uint32_t)io));
-    uint8_t *out0 = a.out + (((uint64_t)MZ_UNIFORM((uint32_t)(oo >> 32)) << 32) | MZ_UNIFORM((uint32_t)oo));
+    const uint8_t *in = a.in + MZ_UNIFORM64(io);
+    uint8_t *out0 = a.out + MZ_UNIFORM64(oo);
     const uint32_t len = MZ_UNIFORM(a.in_len[0]);
     for (;;) {
         uint32_t b;

@@ -980,7 +980,7 @@ def test_deflate_default_class_roundtrip(emu):
 
 
 def test_deflate_classes_fuzz(emu):
-    """Round trips of the lazy class and the cost parse (deflate_core.h, deflate_select.inc) over the shapes that break
+    """Round trips of the lazy class and the cost parse (deflate_core.h, deflate_select.inc, lz77_core.h, lz77_select.inc) over the shapes that break
     parsers: every length around the step (64), the group (4) and the match limits (3, 4, 258, 259), runs, short periods,
     two-symbol noise, incompressible bytes, blocks beyond 64 KiB, final and non-final pieces, small windows."""
     import random
