@@ -34,6 +34,7 @@ typedef struct mzhip_crc_tables {
     uint32_t x64[64];       /* x^(512*j) mod P                          */
     uint32_t mul4[4][256];  /* (v at byte b of the register) * x^(8*4032) mod P: the super-tile advance as four lookups */
     uint32_t slice[4][256]; /* slicing-by-4 tables: slice[0] = byte_tab, slice[k][i] = slice[k-1][i] advanced by one zero byte */
+    uint32_t mul4k[4][256]; /* (v at byte b of the register) * x^(8*4096) mod P: the advance over one WHOLE super-tile (MZ_CRC_FOLD_SUPER_BT_GROUP) */
 } mzhip_crc_tables;
 
 /* host-side generation (plain arithmetic on 32-bit polynomials) */
@@ -76,6 +77,9 @@ static inline void mzhip_crc_tables_init(mzhip_crc_tables *t) {
     for (int j = 0; j < 64; j++) t->x64[j] = mzhip_xpow8_host(64u * (uint32_t)j);
     for (int b = 0; b < 4; b++)
         for (uint32_t n = 0; n < 256; n++) t->mul4[b][n] = mzhip_gf2_mul_host(n << (8 * b), t->kx4[0]);
+    k = mzhip_xpow8_host(MZ_CRC_SUPER);
+    for (int b = 0; b < 4; b++)
+        for (uint32_t n = 0; n < 256; n++) t->mul4k[b][n] = mzhip_gf2_mul_host(n << (8 * b), k);
     for (uint32_t n = 0; n < 256; n++) t->slice[0][n] = t->byte_tab[n];
     for (int k2 = 1; k2 < 4; k2++)
         for (uint32_t n = 0; n < 256; n++) t->slice[k2][n] = (t->slice[k2 - 1][n] >> 8) ^ t->byte_tab[t->slice[k2 - 1][n] & 255];
@@ -200,6 +204,68 @@ MZ_DEV uint32_t mz_crc_advance_gm(uint32_t r, const uint32_t *mul4) {
         }                                                                                  \
         (done) += MZ_CRC_SUPER;                                                            \
     }
+/* The same fold with MZ_CRC_CHAINS (C) super-tiles of a lane in flight (K1's per-chunk call sites).  Inside one tile a lane's
+ * 64 look-ups are one dependent chain: each address is the previous look-up's result, an LDS round trip per step.  CRC is
+ * GF(2)-linear: fold64(x, data) = Z64(x) ^ fold64(0, data), so tile t + i of a group can be folded from register 0 while tile t
+ * is folded from the accumulator, C look-ups in flight at a time, and the results are combined in Horner form with the advance
+ * over a WHOLE super-tile (mul4k: x^(8*4096) = the 4032 bytes of the other lanes and the lane's own 64):
+ *     acc = ADV4K(acc) ^ d1; acc = ADV4K(acc) ^ d2; ...
+ * The same 64 look-ups and four gathers per lane and tile as the single fold, and the same accumulators at every group
+ * boundary, bit for bit.  Only whole groups are folded: up to C - 1 complete tiles stay pending (they leave with a later
+ * group, or one at a time with MZ_CRC_FOLD_SUPER_BT in front of MZ_CRC_FINISH_SUPER_BT).  C = 1 is the single fold.
+ * Config 2 (100 000 x 64 KiB), five interleaved runs each (profiles/r7): C = 1 382.9 - 385.7 GiB/s, C = 2 401.9 - 405.0
+ * (+5.0 %), C = 4 399.6 - 404.5 -- and C = 4 costs k_inflate_batch 16 bytes of scratch more (56 for 40; without MZ_NOUNROLL on
+ * the 16-byte steps 140).  The default is 2. */
+#ifndef MZ_CRC_CHAINS
+#define MZ_CRC_CHAINS 2
+#endif
+#if MZ_CRC_CHAINS != 1 && MZ_CRC_CHAINS != 2 && MZ_CRC_CHAINS != 4
+#error "MZ_CRC_CHAINS must be 1, 2 or 4"
+#endif
+#if MZ_CRC_CHAINS == 4
+#define MZ_CRC_GROUP_UNR MZ_NOUNROLL /* (unrolled, the four tiles' 16-byte loads of all four steps are hoisted and spill) */
+#else
+#define MZ_CRC_GROUP_UNR
+#endif
+#define MZ_CRC_GROUP_LB 16u /* bytes of a tile per load */
+#define MZ_CRC_ADVANCE_SUPER4K(r, kxp) mz_crc_advance_gm((r), (const uint32_t *)((const uint8_t *)(kxp) + (offsetof(mzhip_crc_tables, mul4k) - offsetof(mzhip_crc_tables, kx4))))
+#if MZ_CRC_CHAINS == 1
+#define MZ_CRC_FOLD_SUPER_BT_GROUP(acc, done, buf, upto, tab, kx4) MZ_CRC_FOLD_SUPER_BT(acc, done, buf, upto, tab, kx4)
+#else
+#define MZ_CRC_FOLD_SUPER_BT_GROUP(acc, done, buf, upto, tab, kx4)                         \
+    while ((uint64_t)(done) + MZ_CRC_CHAINS * MZ_CRC_SUPER <= (uint64_t)(upto)) {          \
+        MZ_LANES {                                                                         \
+            const uint8_t *_p = (buf) + (done) + 64u * (uint32_t)lane;                     \
+            uint32_t _c[MZ_CRC_CHAINS];                                                    \
+            _c[0] = P(acc);                                                                \
+            if ((done) != 0) _c[0] = MZ_CRC_ADVANCE_SUPER(_c[0], (kx4));                   \
+_Pragma("unroll")                                                                          \
+            for (int _i = 1; _i < MZ_CRC_CHAINS; _i++) _c[_i] = 0u;                        \
+            MZ_CRC_GROUP_UNR                                                               \
+            for (uint32_t _k = 0; _k < 64u; _k += MZ_CRC_GROUP_LB) {                       \
+                uint32_t _q[MZ_CRC_CHAINS][MZ_CRC_GROUP_LB / 4u];                          \
+_Pragma("unroll")                                                                          \
+                for (int _i = 0; _i < MZ_CRC_CHAINS; _i++)                                 \
+                    __builtin_memcpy(_q[_i], _p + MZ_CRC_SUPER * (uint32_t)_i + _k, MZ_CRC_GROUP_LB); /* one load each */ \
+_Pragma("unroll")                                                                          \
+                for (uint32_t _d = 0; _d < MZ_CRC_GROUP_LB / 4u; _d++) {                   \
+_Pragma("unroll")                                                                          \
+                    for (int _i = 0; _i < MZ_CRC_CHAINS; _i++) _c[_i] ^= _q[_i][_d];       \
+_Pragma("unroll")                                                                          \
+                    for (int _b = 0; _b < 4; _b++)                                         \
+_Pragma("unroll")                                                                          \
+                        for (int _i = 0; _i < MZ_CRC_CHAINS; _i++) /* the chains' look-ups, interleaved in program order */ \
+                            _c[_i] = (tab)[_c[_i] & 255u] ^ (_c[_i] >> 8);                 \
+                }                                                                          \
+            }                                                                              \
+            uint32_t _r = _c[0];                                                           \
+_Pragma("unroll")                                                                          \
+            for (int _i = 1; _i < MZ_CRC_CHAINS; _i++) _r = MZ_CRC_ADVANCE_SUPER4K(_r, (kx4)) ^ _c[_i]; \
+            P(acc) = _r;                                                                   \
+        }                                                                                  \
+        (done) += MZ_CRC_CHAINS * MZ_CRC_SUPER;                                            \
+    }
+#endif
 /* finish a CRC whose complete super-tiles of buf[0 .. n) were folded by MZ_CRC_FOLD_SUPER_BT: collapse the 64 strips,
  * then the remaining < 4 KiB with 1 KiB tiles and the byte-granular tail.  Result (uniform) in `result`. */
 #define MZ_CRC_FINISH_SUPER_BT(result, acc, tmp, done, buf, n, tab, tabs)                  \

@@ -185,7 +185,7 @@
         out_pos += Tb;
         MZ_PROF_MARK(8); /* store */
 #if !(MZ_ABLATE & 4)
-        MZ_CRC_FOLD_SUPER_BT(crc_acc, crc_done, out + crc_base, out_pos - crc_base, crc_tab, tabs->kx4);
+        MZ_CRC_FOLD_SUPER_BT_GROUP(crc_acc, crc_done, out + crc_base, out_pos - crc_base, crc_tab, tabs->kx4);
 #endif
         MZ_PROF_MARK(9); /* crc */
     }

@@ -430,7 +430,38 @@ MZ_DEV void mz_copy32(uint8_t *dst, const uint8_t *src, uint32_t n) {
 }
 /* the same inside the staging area, where the source may end less than n (but at least 8) bytes in front of the
  * destination: 8-byte steps in order, each one reading only what the steps before it (or earlier pieces) wrote */
+#ifndef MZ_NEAR_TAIL
+#define MZ_NEAR_TAIL 0 /* 1: the last n & 7 bytes without a chain of 4-, 2- and 1-byte load -> store pairs (below).  Measured
+                          SLOWER: config 2 376.5 - 381.3 GiB/s against 382.9 - 385.7 (-1.5 %, profiles/r7; not profiled further --
+                          the kernel is short of issue slots, and this form has more exec brackets than the chain it replaces) */
+#endif
 MZ_DEV void mz_copy32_seq(uint8_t *dst, const uint8_t *src, uint32_t n) {
+#if MZ_NEAR_TAIL
+    /* The body steps stay in order.  The tail cannot alias itself: the distance is at least 8 and the tail at most 7 bytes.
+     *   n >= 8, n & 7 != 0: ONE 8-byte pair at offset n - 8 behind the body steps.  Its source ends at or before its own
+     *                       destination and lies below dst + n - 8, all of it written by the body steps or by earlier pieces;
+     *                       it writes the bytes in front of the tail once more with the values they hold.
+     *   n < 8:              source and destination do not overlap: the three loads first, then the three stores.
+     * The first 8-byte load and the small loads are all issued before the first store (the lanes of a round are one or the
+     * other). */
+    uint64_t v0 = 0;
+    uint32_t t4 = 0, t2 = 0, t1 = 0;
+    if (n >= 8u) v0 = mz_ld8(src);
+    if (n < 8u && (n & 4u)) t4 = mz_ld4(src);
+    if (n < 8u && (n & 2u)) t2 = mz_ld2(src + (n & 4u));
+    if (n < 8u && (n & 1u)) t1 = src[n - 1u];
+    if (n >= 8u) {
+        mz_st8(dst, v0);
+#pragma unroll
+        for (uint32_t k = 1; k < 4u; k++)
+            if (8u * k + 8u <= n) mz_st8(dst + 8u * k, mz_ld8(src + 8u * k));
+        if (n & 7u) mz_st8(dst + (n - 8u), mz_ld8(src + (n - 8u)));
+    } else {
+        if (n & 4u) mz_st4(dst, t4);
+        if (n & 2u) mz_st2(dst + (n & 4u), t2);
+        if (n & 1u) dst[n - 1u] = (uint8_t)t1;
+    }
+#else
     const uint32_t n8 = n & ~7u;
 #pragma unroll
     for (uint32_t k = 0; k < 4u; k++)
@@ -438,6 +469,7 @@ MZ_DEV void mz_copy32_seq(uint8_t *dst, const uint8_t *src, uint32_t n) {
     if (n & 4u) mz_st4(dst + n8, mz_ld4(src + n8));
     if (n & 2u) mz_st2(dst + n8 + (n & 4u), mz_ld2(src + n8 + (n & 4u)));
     if (n & 1u) dst[n - 1u] = src[n - 1u];
+#endif
 }
 
 /* One step of a chase-window walk (inflate_chase.inc) as its RECORD.  A DEFLATE token walk started at an arbitrary bit falls
@@ -686,7 +718,7 @@ MZ_DEV void mz_inflate_entry(const uint8_t *in, uint32_t in_total, uint8_t *out,
                 status = MZHIP_BUF_ERROR;
                 goto finish;
             }
-            if (!par) MZ_CRC_FOLD_SUPER_BT(crc_acc, crc_done, out + crc_base, out_pos - crc_base, crc_tab, tabs->kx4);
+            if (!par) MZ_CRC_FOLD_SUPER_BT_GROUP(crc_acc, crc_done, out + crc_base, out_pos - crc_base, crc_tab, tabs->kx4);
             in_header = 0;
             hdr_bit = bitpos;
             par_blocks++;

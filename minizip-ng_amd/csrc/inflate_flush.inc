@@ -140,7 +140,7 @@
             }
         }
         out_pos += total;
-        MZ_CRC_FOLD_SUPER_BT(crc_acc, crc_done, out + crc_base, out_pos - crc_base, crc_tab, tabs->kx4);
+        MZ_CRC_FOLD_SUPER_BT_GROUP(crc_acc, crc_done, out + crc_base, out_pos - crc_base, crc_tab, tabs->kx4);
         if (part_bits) {
             bitpos = qbit + part_bits;
             status = MZHIP_OUT_FULL;
