@@ -244,39 +244,36 @@ static int32_t inflate_window_host(const uint8_t *in, uint32_t in_len, uint8_t *
                                        const mzhip_inflate_state *state_in, mzhip_inflate_state *state_out, uint32_t *out_len,
                                        uint32_t *in_used, uint32_t *crc, uint32_t *adler, uint32_t seg_first, uint32_t seg_stride,
                                        uint32_t *seg_crc, uint32_t seg_cap, uint32_t *nseg) {
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
     const uint32_t hist = state_in ? state_in->out_pos : 0u;
-    if (hist > buf_cap) return -102; /* MZ_PARAM_ERROR */
-    // layout: [meta 128 B][in (16-aligned)][buf][segment arrays]
-    const size_t in_pad = ((size_t)in_len + 15) & ~(size_t)15;
-    const size_t buf_pad = ((size_t)buf_cap + 16 + 15) & ~(size_t)15;
-    const size_t seg_max = (seg_stride && seg_crc) ? (size_t)buf_cap / seg_stride + 3 : 0;
-    const size_t ck_max = adler ? (size_t)buf_cap / 65536u + 3 : 0;
-    const size_t total = 128 + in_pad + buf_pad + seg_max * 16 + ck_max * 16;
-    if (nseg) *nseg = 0;
-    if (adler) *adler = 1u;
-    Staging sc;
-    rc = sc.get(c, total);
-    if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
     struct Meta {
         uint64_t in_off, out_off;
         uint32_t in_len, out_cap, out_len, in_used, crc;
         int32_t status;
         mzhip_inflate_state rs, st;
-    } m;
-    memset(&m, 0, sizeof(m));
-    m.in_off = 128;
-    m.out_off = 128 + in_pad;
+    };
+    HostCall<Meta> hc;
+    int32_t rc = ctx_for_current(&hc.c);
+    if (rc) return rc;
+    if (hist > buf_cap) return -102; /* MZ_PARAM_ERROR */
+    // layout: [meta][in][buf][segment arrays][checksum arrays]
+    const size_t seg_max = (seg_stride && seg_crc) ? (size_t)buf_cap / seg_stride + 3 : 0;
+    const size_t ck_max = adler ? (size_t)buf_cap / 65536u + 3 : 0;
+    Meta &m = hc.m;
+    m.in_off = hc.take(in_len);
+    m.out_off = hc.take((size_t)buf_cap + 16);
+    const size_t o_seg = hc.take(seg_max * 16), o_ck = hc.take(ck_max * 16);
     m.in_len = in_len;
     m.out_cap = buf_cap;
     if (state_in) memcpy(&m.rs, state_in, sizeof(m.rs));
-    HIP_TRY(mz_h2d(base, &m, sizeof(m)));
-    if (in_len) HIP_TRY(mz_h2d(base + 128, in, in_len));
-    if (hist) HIP_TRY(mz_h2d(base + m.out_off, buf, hist));
-    Meta *dm = (Meta *)base;
+    give(nseg, 0u);
+    give(adler, 1u);
+    rc = hc.begin();
+    if (rc) return rc;
+    uint8_t *base = hc.at(0);
+    Meta *dm = hc.dm;
+    HIP_TRY(hc.put_meta());
+    if (in_len) HIP_TRY(mz_h2d(hc.at(m.in_off), in, in_len));
+    if (hist) HIP_TRY(mz_h2d(hc.at(m.out_off), buf, hist));
     rc = mzhip_inflate_resume_batch(base, &dm->in_off, &dm->in_len, base, &dm->out_off, &dm->out_cap, 1, &dm->out_len,
                                     &dm->in_used, &dm->crc, &dm->status, (const mzhip_inflate_state *)&dm->rs,
                                     /* no state asked for = the last call of a stream that ended short: the kernel then drops the
@@ -285,68 +282,83 @@ static int32_t inflate_window_host(const uint8_t *in, uint32_t in_len, uint8_t *
                                      * (found by tests/test_gpu_dropin.py::test_truncation_accounting_window_mode, round 4) */
                                     state_out ? (mzhip_inflate_state *)&dm->st : nullptr, MZ_HOST_STREAM);
     if (rc) return rc;
-    HIP_TRY(mz_d2h(&m, base, sizeof(m)));
-    if (m.out_len > hist) HIP_TRY(mz_d2h(buf + hist, base + m.out_off + hist, m.out_len - hist));
+    HIP_TRY(hc.fetch_meta());
+    if (m.out_len > hist) HIP_TRY(mz_d2h(buf + hist, hc.at(m.out_off) + hist, m.out_len - hist));
     if (seg_max && m.out_len > hist) {
-        rc = window_piece_crcs(base, m.out_off, hist, m.out_len, seg_first, seg_stride, seg_crc, seg_cap, nseg, base + 128 + in_pad + buf_pad,
-                               seg_max);
+        rc = window_piece_crcs(base, m.out_off, hist, m.out_len, seg_first, seg_stride, seg_crc, seg_cap, nseg, hc.at(o_seg), seg_max);
         if (rc) return rc;
     }
     if (adler && m.out_len > hist) {
-        rc = window_checksums(base, m.out_off, hist, m.out_len, nullptr, adler, base + 128 + in_pad + buf_pad + seg_max * 16, ck_max);
+        rc = window_checksums(base, m.out_off, hist, m.out_len, nullptr, adler, hc.at(o_ck), ck_max);
         if (rc) return rc;
     }
-    if (out_len) *out_len = m.out_len;
-    if (in_used) *in_used = m.in_used;
-    if (crc) *crc = m.crc;
+    give(out_len, m.out_len);
+    give(in_used, m.in_used);
+    give(crc, m.crc);
     if (state_out) memcpy(state_out, &m.st, sizeof(m.st));
     return m.status;
 }
 
-static int32_t inflate_whole_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, uint32_t *out_len,
-                            uint32_t *in_used, uint32_t *crc, uint32_t *adler) {
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    // layout: [meta 64 B][in (16-aligned)][out]
-    const size_t in_pad = ((size_t)in_len + 15) & ~(size_t)15;
-    const size_t total = 64 + in_pad + out_cap + 16;
-    Staging sc;
-    rc = sc.get(c, total);
-    if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
-    struct Meta {
-        uint64_t in_off, out_off;
-        uint32_t in_len, out_cap, out_len, in_used, crc;
-        int32_t status;
-        uint32_t adler, pad;
-    } m;
-    memset(&m, 0, sizeof(m));
-    m.in_off = 64;
-    m.out_off = 64 + in_pad;
+} // extern "C"
+
+// One whole entry from a host buffer through a batch launcher, as a batch of one: `launch` gets the staging buffer (what the
+// meta block's offsets count from) and the meta block on the device.  max_out is the LZMA family's; an Adler-32 is asked for by
+// inflate's zlib wrapper only.
+struct WholeMeta {
+    uint64_t in_off, out_off;
+    int64_t max_out;
+    uint32_t in_len, out_cap, out_len, in_used, crc;
+    int32_t status;
+    uint32_t adler, pad;
+};
+template <class Launch>
+static int32_t decode_whole_host(Launch launch, const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, int64_t max_out,
+                                 uint32_t *out_len, uint32_t *in_used, uint32_t *crc, uint32_t *adler) {
+    HostCall<WholeMeta> hc;
+    WholeMeta &m = hc.m;
+    m.in_off = hc.take(in_len);
+    m.out_off = hc.take((size_t)out_cap + 16);
+    m.max_out = max_out;
     m.in_len = in_len;
     m.out_cap = out_cap;
-    HIP_TRY(mz_h2d(base, &m, sizeof(m)));
-    if (in_len) HIP_TRY(mz_h2d(base + 64, in, in_len));
-    Meta *dm = (Meta *)base;
-    rc = mzhip_inflate_batch(base, &dm->in_off, &dm->in_len, base, &dm->out_off, &dm->out_cap, 1, &dm->out_len,
-                             &dm->in_used, &dm->crc, &dm->status, MZ_HOST_STREAM);
+    int32_t rc = hc.begin();
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
+    uint8_t *base = hc.at(0);
+    WholeMeta *dm = hc.dm;
+    HIP_TRY(hc.put_meta());
+    if (in_len) HIP_TRY(mz_h2d(hc.at(m.in_off), in, in_len));
+    rc = launch(base, dm);
+    if (rc) return rc;
     if (adler) { /* zlib wrapper: Adler-32 of the decoded bytes, reduced on the device as well */
-        HIP_TRY(mz_d2h(&m, base, sizeof(m)));
+        HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
         rc = mzhip_adler32_batch(base, &dm->out_off, &dm->out_len, 1, &dm->adler, MZ_HOST_STREAM);
         if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
     }
-    HIP_TRY(mz_d2h(&m, base, sizeof(m)));
-    if (m.out_len && out) HIP_TRY(mz_d2h(out, base + m.out_off, m.out_len));
-    if (out_len) *out_len = m.out_len;
-    if (in_used) *in_used = m.in_used;
-    if (crc) *crc = m.crc;
-    if (adler) *adler = m.adler;
+    HIP_TRY(hc.wait_fetch_meta());
+    if (m.out_len && out) HIP_TRY(mz_d2h(out, hc.at(m.out_off), m.out_len));
+    give(out_len, m.out_len);
+    give(in_used, m.in_used);
+    give(crc, m.crc);
+    give(adler, m.adler);
     return m.status;
 }
+// (inflate and bzip2 launchers take the same arguments)
+#define MZ_LAUNCH_ONE(fn)                                                                                                       \
+    [](uint8_t *base, WholeMeta *dm) {                                                                                          \
+        return fn(base, &dm->in_off, &dm->in_len, base, &dm->out_off, &dm->out_cap, 1, &dm->out_len, &dm->in_used, &dm->crc, \
+                  &dm->status, MZ_HOST_STREAM);                                                                                 \
+    }
+static int32_t lzma_family_host(int xz, const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, int64_t max_out,
+                                uint32_t *out_len, uint32_t *in_used, uint32_t *crc) {
+    return decode_whole_host(
+        [xz](uint8_t *base, WholeMeta *dm) {
+            return (xz ? mzhip_xz_batch : mzhip_lzma_batch)(base, &dm->in_off, &dm->in_len, base, &dm->out_off, &dm->out_cap, &dm->max_out, 1,
+                                                            &dm->out_len, &dm->in_used, &dm->crc, &dm->status, MZ_HOST_STREAM);
+        },
+        in, in_len, out, out_cap, max_out, out_len, in_used, crc, nullptr);
+}
+
+extern "C" {
 
 /* include/mzhip.h: one entry point for a whole entry and for one window of it.  Fields behind `size` read as zero / NULL, so a
  * caller compiled against an older (shorter) struct keeps working when fields are appended. */
@@ -357,48 +369,10 @@ int32_t mzhip_inflate_host_a(const mzhip_inflate_host_args *ap) {
     memcpy(&a, ap, ap->size < sizeof(a) ? ap->size : sizeof(a));
     if (!a.state_in && !a.state_out) {
         if (a.nseg) *a.nseg = 0; /* (no pieces of a whole entry: the READ shim asks the per-call CRCs of a window only) */
-        return inflate_whole_host(a.in, a.in_len, a.buf, a.buf_cap, a.out_len, a.in_used, a.crc, a.adler);
+        return decode_whole_host(MZ_LAUNCH_ONE(mzhip_inflate_batch), a.in, a.in_len, a.buf, a.buf_cap, 0, a.out_len, a.in_used, a.crc, a.adler);
     }
     return inflate_window_host(a.in, a.in_len, a.buf, a.buf_cap, a.state_in, a.state_out, a.out_len, a.in_used, a.crc, a.adler,
                                a.seg_first, a.seg_stride, a.seg_crc, a.seg_cap, a.nseg);
-}
-
-static int32_t lzma_family_host(int xz, const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, int64_t max_out,
-                                uint32_t *out_len, uint32_t *in_used, uint32_t *crc) {
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    const size_t in_pad = ((size_t)in_len + 15) & ~(size_t)15;
-    const size_t total = 64 + in_pad + out_cap + 16;
-    Staging sc;
-    rc = sc.get(c, total);
-    if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
-    struct Meta {
-        uint64_t in_off, out_off;
-        int64_t max_out;
-        uint32_t in_len, out_cap, out_len, in_used, crc;
-        int32_t status;
-    } m;
-    memset(&m, 0, sizeof(m));
-    m.in_off = 64;
-    m.out_off = 64 + in_pad;
-    m.max_out = max_out;
-    m.in_len = in_len;
-    m.out_cap = out_cap;
-    HIP_TRY(mz_h2d(base, &m, sizeof(m)));
-    if (in_len) HIP_TRY(mz_h2d(base + 64, in, in_len));
-    Meta *dm = (Meta *)base;
-    rc = (xz ? mzhip_xz_batch : mzhip_lzma_batch)(base, &dm->in_off, &dm->in_len, base, &dm->out_off, &dm->out_cap, &dm->max_out, 1,
-                           &dm->out_len, &dm->in_used, &dm->crc, &dm->status, MZ_HOST_STREAM);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
-    HIP_TRY(mz_d2h(&m, base, sizeof(m)));
-    if (m.out_len && out) HIP_TRY(mz_d2h(out, base + m.out_off, m.out_len));
-    if (out_len) *out_len = m.out_len;
-    if (in_used) *in_used = m.in_used;
-    if (crc) *crc = m.crc;
-    return m.status;
 }
 
 int32_t mzhip_lzma_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, int64_t max_out,
@@ -414,38 +388,7 @@ int32_t mzhip_xz_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t
 // One bzip2 stream (ZIP method 12) from a host buffer.
 int32_t mzhip_bzip2_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, uint32_t *out_len, uint32_t *in_used,
                          uint32_t *crc) {
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    const size_t in_pad = ((size_t)in_len + 15) & ~(size_t)15;
-    const size_t total = 64 + in_pad + out_cap + 16;
-    Staging sc;
-    rc = sc.get(c, total);
-    if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
-    struct Meta {
-        uint64_t in_off, out_off;
-        uint32_t in_len, out_cap, out_len, in_used, crc;
-        int32_t status;
-    } m;
-    memset(&m, 0, sizeof(m));
-    m.in_off = 64;
-    m.out_off = 64 + in_pad;
-    m.in_len = in_len;
-    m.out_cap = out_cap;
-    HIP_TRY(mz_h2d(base, &m, sizeof(m)));
-    if (in_len) HIP_TRY(mz_h2d(base + 64, in, in_len));
-    Meta *dm = (Meta *)base;
-    rc = mzhip_bzip2_batch(base, &dm->in_off, &dm->in_len, base, &dm->out_off, &dm->out_cap, 1, &dm->out_len, &dm->in_used, &dm->crc,
-                           &dm->status, MZ_HOST_STREAM);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
-    HIP_TRY(mz_d2h(&m, base, sizeof(m)));
-    if (m.out_len && out) HIP_TRY(mz_d2h(out, base + m.out_off, m.out_len));
-    if (out_len) *out_len = m.out_len;
-    if (in_used) *in_used = m.in_used;
-    if (crc) *crc = m.crc;
-    return m.status;
+    return decode_whole_host(MZ_LAUNCH_ONE(mzhip_bzip2_batch), in, in_len, out, out_cap, 0, out_len, in_used, crc, nullptr);
 }
 
 // One ZIP method-14 payload from a host buffer.
@@ -456,37 +399,31 @@ int32_t mzhip_lzma_encode_host(const uint8_t *in, uint32_t in_len, uint8_t *out,
 
 int32_t mzhip_lzma_encode_host_preset(const uint8_t *in, uint32_t in_len, int32_t preset, uint8_t *out, uint32_t out_cap,
                                       uint32_t *out_len, uint32_t *crc) {
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    const size_t in_pad = ((size_t)in_len + 63) & ~(size_t)63;
-    const uint32_t cap = in_len + in_len / 8 + 1024;
-    Staging sc;
-    rc = sc.get(c, 64 + in_pad + cap);
-    if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
     struct Meta {
         uint64_t in_off, out_off;
         uint32_t in_len, out_cap, out_len, crc;
         int32_t status;
-    } m;
-    memset(&m, 0, sizeof(m));
-    m.in_off = 64;
-    m.out_off = 64 + in_pad;
+    };
+    HostCall<Meta> hc;
+    Meta &m = hc.m;
     m.in_len = in_len;
-    m.out_cap = cap;
-    HIP_TRY(mz_h2d(base, &m, sizeof(m)));
-    if (in_len) HIP_TRY(mz_h2d(base + 64, in, in_len));
-    Meta *dm = (Meta *)base;
+    m.out_cap = in_len + in_len / 8 + 1024;
+    m.in_off = hc.take(in_len, 64);
+    m.out_off = hc.take(m.out_cap, 64);
+    int32_t rc = hc.begin();
+    if (rc) return rc;
+    uint8_t *base = hc.at(0);
+    Meta *dm = hc.dm;
+    HIP_TRY(hc.put_meta());
+    if (in_len) HIP_TRY(mz_h2d(hc.at(m.in_off), in, in_len));
     rc = mzhip_lzma_encode_batch_preset(base, &dm->in_off, &dm->in_len, in_len, base, &dm->out_off, &dm->out_cap, nullptr, 1,
                                         preset, &dm->out_len, &dm->crc, &dm->status, MZ_HOST_STREAM);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
-    HIP_TRY(mz_d2h(&m, base, sizeof(m)));
+    HIP_TRY(hc.wait_fetch_meta());
     if (m.status == 0 && m.out_len > out_cap) m.status = MZHIP_STATUS_OUT_FULL;
-    if (m.status == 0 && m.out_len) HIP_TRY(mz_d2h(out, base + m.out_off, m.out_len));
-    if (out_len) *out_len = m.out_len;
-    if (crc) *crc = m.crc;
+    if (m.status == 0 && m.out_len) HIP_TRY(mz_d2h(out, hc.at(m.out_off), m.out_len));
+    give(out_len, m.out_len);
+    give(crc, m.crc);
     return m.status;
 }
 
@@ -498,7 +435,6 @@ int32_t mzhip_xz_encode_finish_host(const uint64_t *unpadded_size, const uint64_
         while (v >= 0x80) { idx.push_back((uint8_t)(v | 0x80)); v >>= 7; }
         idx.push_back((uint8_t)v);
     };
-    auto le32 = [](uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); };
     idx.push_back(0x00);
     vli(nblocks);
     for (uint32_t i = 0; i < nblocks; i++) {
@@ -507,13 +443,13 @@ int32_t mzhip_xz_encode_finish_host(const uint64_t *unpadded_size, const uint64_
     }
     while (idx.size() & 3u) idx.push_back(0);
     uint8_t c4[4];
-    le32(c4, mzhip_crc32_host(0, idx.data(), idx.size()));
+    put_le32(c4, mzhip_crc32_host(0, idx.data(), idx.size()));
     idx.insert(idx.end(), c4, c4 + 4);
     uint8_t ft[12];
-    le32(ft + 4, (uint32_t)(idx.size() / 4 - 1));
+    put_le32(ft + 4, (uint32_t)(idx.size() / 4 - 1));
     ft[8] = 0x00;
     ft[9] = 0x01;
-    le32(ft, mzhip_crc32_host(0, ft + 4, 6));
+    put_le32(ft, mzhip_crc32_host(0, ft + 4, 6));
     ft[10] = 'Y';
     ft[11] = 'Z';
     if (idx.size() + 12 > out_cap) return MZHIP_STATUS_OUT_FULL;

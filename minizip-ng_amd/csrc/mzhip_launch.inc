@@ -987,38 +987,35 @@ int32_t mzhip_inflate_parallel_host(const uint8_t *in, uint32_t in_len, uint8_t 
     if (state_in && (state_in->flags & 1u) && state_in->bit != state_in->hdr_bit) return 0; /* (inside a block: stream order) */
     if (hist > buf_cap) return -102;
     if (in_len >= (1u << 29) || in_len < 64u) return 0; /* (bit positions are 32 bits wide) */
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
     const int wgs = par_wgs_per_cu();
-    // layout: [in][buf][source map: 4 B per byte of buf][candidates][bits][pos][results: 16 B each][two counters][segment arrays]
-    const size_t in_pad = ((size_t)in_len + 64 + 15) & ~(size_t)15;
-    const size_t buf_pad = ((size_t)buf_cap + 16 + 15) & ~(size_t)15;
+    // layout: [in][buf][source map: 4 B per byte of buf][candidates][bits][pos][results: 16 B each][two counters][segment arrays][checksum arrays]
+    const size_t buf_room = ((size_t)buf_cap + 16 + 15) & ~(size_t)15;
     const uint32_t cap = in_len / 16u + 4096u;
     const size_t seg_max = (seg_stride && seg_crc) ? (size_t)buf_cap / seg_stride + 3 : 0;
     const size_t ck_max = (crc || adler) ? (size_t)buf_cap / 65536u + 3 : 0;
-    const size_t o_buf = in_pad, o_ptr = o_buf + buf_pad, o_cands = o_ptr + 4 * buf_pad, o_bits = o_cands + 4 * (size_t)(cap + 4),
-                 o_pos = o_bits + 4 * (size_t)(cap + 4), o_res = o_pos + 4 * (size_t)(cap + 4), o_count = o_res + 16 * (size_t)(cap + 4),
-                 o_seg = o_count + 16, o_ck = o_seg + seg_max * 16, total = o_ck + ck_max * 16;
-    Staging sc;
-    rc = sc.get(c, total);
+    StagedCall hc;
+    const size_t o_in = hc.take((size_t)in_len + 64), o_buf = hc.take(buf_room), o_ptr = hc.take(4 * buf_room), o_cands = hc.take(4 * (size_t)(cap + 4)),
+                 o_bits = hc.take(4 * (size_t)(cap + 4)), o_pos = hc.take(4 * (size_t)(cap + 4)), o_res = hc.take(16 * (size_t)(cap + 4)),
+                 o_count = hc.take(16), o_seg = hc.take(seg_max * 16), o_ck = hc.take(ck_max * 16);
+    int32_t rc = hc.begin();
     if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
-    HIP_TRY(mz_h2d(base, in, in_len));
-    HIP_TRY(hipMemsetAsync(base + in_len, 0, in_pad - in_len, MZ_HOST_STREAM));
-    if (hist) HIP_TRY(mz_h2d(base + o_buf, buf, hist));
+    DeviceCtx *c = hc.c;
+    uint8_t *base = hc.at(0), *d_in = hc.at(o_in);
+    HIP_TRY(mz_h2d(d_in, in, in_len));
+    HIP_TRY(hipMemsetAsync(d_in + in_len, 0, (o_buf - o_in) - in_len, MZ_HOST_STREAM)); /* (up to the window) */
+    if (hist) HIP_TRY(mz_h2d(hc.at(o_buf), buf, hist));
     DevParBackend be;
     be.c = c;
     be.s = MZ_HOST_STREAM;
-    be.d_in = base;
+    be.d_in = d_in;
     be.in_len = in_len;
-    be.d_buf = base + o_buf;
-    be.d_ptr = (uint32_t *)(base + o_ptr);
-    be.d_cands = (uint32_t *)(base + o_cands);
-    be.d_bits = (uint32_t *)(base + o_bits);
-    be.d_pos = (uint32_t *)(base + o_pos);
-    be.d_res = (uint32_t *)(base + o_res);
-    be.d_count = (uint32_t *)(base + o_count);
+    be.d_buf = hc.at(o_buf);
+    be.d_ptr = (uint32_t *)hc.at(o_ptr);
+    be.d_cands = (uint32_t *)hc.at(o_cands);
+    be.d_bits = (uint32_t *)hc.at(o_bits);
+    be.d_pos = (uint32_t *)hc.at(o_pos);
+    be.d_res = (uint32_t *)hc.at(o_res);
+    be.d_count = (uint32_t *)hc.at(o_count);
     be.cap = cap;
     be.wgs_per_cu = wgs;
     const int trace = par_trace();
@@ -1029,14 +1026,14 @@ int32_t mzhip_inflate_parallel_host(const uint8_t *in, uint32_t in_len, uint8_t 
     rc = mz_parallel_window(be, in_len, buf_cap, start, hist, &w);
     const double t2 = DevParBackend::now();
     if (rc == 0 && w.blocks) {
-        if (w.total > hist) HIP_TRY(mz_d2h(buf + hist, base + o_buf + hist, w.total - hist));
+        if (w.total > hist) HIP_TRY(mz_d2h(buf + hist, be.d_buf + hist, w.total - hist));
         const double t3 = DevParBackend::now();
         if (seg_max && w.total > hist) {
-            rc = window_piece_crcs(base, o_buf, hist, w.total, seg_first, seg_stride, seg_crc, seg_cap, nseg, base + o_seg, seg_max);
+            rc = window_piece_crcs(base, o_buf, hist, w.total, seg_first, seg_stride, seg_crc, seg_cap, nseg, hc.at(o_seg), seg_max);
             if (rc) return rc;
         }
         if (ck_max) {
-            rc = window_checksums(base, o_buf, hist, w.total, crc, adler, base + o_ck, ck_max);
+            rc = window_checksums(base, o_buf, hist, w.total, crc, adler, hc.at(o_ck), ck_max);
             if (rc) return rc;
         }
         if (trace)
@@ -1076,42 +1073,38 @@ static int32_t lzma_window_host(DeviceCtx *c, const Kernel<Args> &k, const uint8
     static_assert(sizeof(PubState) == sizeof(State), "mzhip.h and the core header describe the same words");
     const uint32_t hist = state_in->out_pos;
     if (hist > buf_cap) return -102;
-    const size_t model_bytes = (MZ_LZMA_MODEL_U16 * sizeof(uint16_t) + 15) & ~(size_t)15;
-    const size_t in_pad = ((size_t)in_len + 15 + 16) & ~(size_t)15;
-    const size_t total = 256 + model_bytes + in_pad + (size_t)buf_cap + 16;
-    Staging sc;
-    const int32_t rc = sc.get(c, total);
-    if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
     struct Meta {
         State rs, st;
         uint32_t out_len, in_used;
         int32_t status;
-    } m;
-    static_assert(sizeof(Meta) <= 256, "meta block");
-    memset(&m, 0, sizeof(m));
+    };
+    HostCall<Meta> hc;
+    hc.c = c;
+    Meta &m = hc.m;
     memcpy(&m.rs, state_in, sizeof(m.rs));
-    uint8_t *d_model = base + 256, *d_in = d_model + model_bytes, *d_buf = d_in + in_pad;
-    HIP_TRY(mz_h2d(base, &m, sizeof(m)));
+    const size_t o_model = hc.take(MZ_LZMA_MODEL_U16 * sizeof(uint16_t)), o_in = hc.take((size_t)in_len + 16), o_buf = hc.take((size_t)buf_cap + 16);
+    const int32_t rc = hc.begin();
+    if (rc) return rc;
+    uint8_t *d_model = hc.at(o_model), *d_in = hc.at(o_in), *d_buf = hc.at(o_buf);
+    Meta *dm = hc.dm;
+    HIP_TRY(hc.put_meta());
     if (state_in->flags & 1u) HIP_TRY(mz_h2d(d_model, model, MZ_LZMA_MODEL_U16 * sizeof(uint16_t)));
     if (in_len) HIP_TRY(mz_h2d(d_in, in, in_len));
     if (hist) HIP_TRY(mz_h2d(d_buf, buf, hist));
-    Meta *dm = (Meta *)base;
     Args a{d_in, in_len, d_buf, buf_cap, &dm->rs, state_out ? &dm->st : nullptr, (uint16_t *)d_model,
            &dm->out_len, &dm->in_used, &dm->status, c->d_tabs};
     set_tab64(a, c->d_tab64, 0);
     hipLaunchKernelGGL(k.fn, dim3(1), dim3(64), 0, MZ_HOST_STREAM, a);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail(k.name, le);
-    HIP_TRY(hipStreamSynchronize(MZ_HOST_STREAM));
-    HIP_TRY(mz_d2h(&m, base, sizeof(m)));
+    HIP_TRY(hc.wait_fetch_meta());
     if (m.out_len > hist && m.out_len <= buf_cap) HIP_TRY(mz_d2h(buf + hist, d_buf + hist, m.out_len - hist));
     if (state_out) {
         memcpy(state_out, &m.st, sizeof(m.st));
         if (m.st.flags & 1u) HIP_TRY(mz_d2h(model, d_model, MZ_LZMA_MODEL_U16 * sizeof(uint16_t)));
     }
-    if (out_len) *out_len = m.out_len;
-    if (in_used) *in_used = m.in_used;
+    give(out_len, m.out_len);
+    give(in_used, m.in_used);
     return m.status;
 }
 
@@ -1148,41 +1141,39 @@ int32_t mzhip_lzma_encode_resume_host(const uint8_t *in, uint32_t in_len, uint32
                                       const mzhip_lzma_enc_state *state_in, mzhip_lzma_enc_state *state_out, void *model,
                                       uint8_t *out, uint32_t out_cap, uint32_t *out_len) {
     static_assert(sizeof(mzhip_lzma_enc_state) == sizeof(mz_lzma_enc_state), "mzhip.h and lzma_enc_core.h describe the same sixteen words");
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
-    if (!model || !state_in || (!last && !state_out) || (uint64_t)skip_blocks * MZ_DEF_BLOCK > in_len) return -102; /* MZ_PARAM_ERROR */
-    const size_t model_bytes = (((LZ_NUM_PROBS + 1u) & ~1u) * sizeof(uint16_t) + 15) & ~(size_t)15;
-    const size_t in_pad = ((size_t)in_len + 63) & ~(size_t)63;
-    const uint32_t cap = in_len + in_len / 8 + 1024;
-    const uint32_t maxb = in_len ? (in_len + MZ_DEF_BLOCK - 1) / MZ_DEF_BLOCK : 1u;
-    /* tokens, the chain pass's links (as many words again) and its table, the token counts, three counters */
-    const size_t tok_bytes = ((size_t)maxb * MZ_DEF_BLOCK * 2u + ((size_t)1 << MZ_LZE_FAR_HBITS)) * sizeof(uint32_t) + (size_t)maxb * sizeof(uint32_t) + 64;
-    Staging sc;
-    rc = sc.get(c, 256 + model_bytes + in_pad + cap + 64 + tok_bytes);
-    if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
     struct Meta {
         mz_lzma_enc_state rs, st;
         uint64_t in_off, out_off;
         uint32_t in_len, out_cap, out_len, crc;
         int32_t status;
-    } m;
-    static_assert(sizeof(Meta) <= 256, "meta block");
-    memset(&m, 0, sizeof(m));
-    memcpy(&m.rs, state_in, sizeof(m.rs));
-    uint8_t *d_model = base + 256, *d_in = d_model + model_bytes, *d_out = d_in + in_pad;
-    m.in_off = (uint64_t)(d_in - base);
-    m.out_off = (uint64_t)(d_out - base);
+    };
+    HostCall<Meta> hc;
+    Meta &m = hc.m;
+    int32_t rc = ctx_for_current(&hc.c);
+    if (rc) return rc;
+    if (!model || !state_in || (!last && !state_out) || (uint64_t)skip_blocks * MZ_DEF_BLOCK > in_len) return -102; /* MZ_PARAM_ERROR */
+    const size_t model_bytes = ((LZ_NUM_PROBS + 1u) & ~1u) * sizeof(uint16_t);
+    const uint32_t cap = in_len + in_len / 8 + 1024;
+    const uint32_t maxb = in_len ? (in_len + MZ_DEF_BLOCK - 1) / MZ_DEF_BLOCK : 1u;
+    /* tokens, the chain pass's links (as many words again) and its table, the token counts, three counters */
+    const size_t tok_bytes = ((size_t)maxb * MZ_DEF_BLOCK * 2u + ((size_t)1 << MZ_LZE_FAR_HBITS)) * sizeof(uint32_t) + (size_t)maxb * sizeof(uint32_t) + 64;
+    const size_t o_model = hc.take(model_bytes);
+    m.in_off = hc.take(in_len, 64);
+    m.out_off = hc.take(cap, 64);
+    const size_t o_tok = hc.take(tok_bytes, 64);
     m.in_len = in_len;
     m.out_cap = cap;
-    HIP_TRY(mz_h2d(base, &m, sizeof(m)));
-    if (state_in->flags & 1u) HIP_TRY(mz_h2d(d_model, model, ((LZ_NUM_PROBS + 1u) & ~1u) * sizeof(uint16_t)));
-    if (in_len) HIP_TRY(mz_h2d(d_in, in, in_len));
-    Meta *dm = (Meta *)base;
+    memcpy(&m.rs, state_in, sizeof(m.rs));
+    rc = hc.begin();
+    if (rc) return rc;
+    uint8_t *base = hc.at(0), *d_model = hc.at(o_model), *d_out = hc.at(m.out_off);
+    Meta *dm = hc.dm;
+    HIP_TRY(hc.put_meta());
+    if (state_in->flags & 1u) HIP_TRY(mz_h2d(d_model, model, model_bytes));
+    if (in_len) HIP_TRY(mz_h2d(hc.at(m.in_off), in, in_len));
     hipStream_t s = MZ_HOST_STREAM;
     LzmaEncResumeArgs r;
-    rc = lz_parse_one_stream(c, s, r.a, base, dm, maxb, skip_blocks, preset, (uint32_t *)(d_out + ((cap + 63u) & ~63u)));
+    rc = lz_parse_one_stream(hc.c, s, r.a, base, dm, maxb, skip_blocks, preset, (uint32_t *)hc.at(o_tok));
     if (rc) return rc;
     r.skip_blocks = skip_blocks;
     r.rs = &dm->rs;
@@ -1191,15 +1182,14 @@ int32_t mzhip_lzma_encode_resume_host(const uint8_t *in, uint32_t in_len, uint32
     hipLaunchKernelGGL(k_lzma_rc_encode_resume, dim3(1), dim3(64), 0, s, r);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail("k_lzma_rc_encode_resume", le);
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(mz_d2h(&m, base, sizeof(m)));
+    HIP_TRY(hc.wait_fetch_meta());
     if (m.status == 0 && m.out_len > out_cap) m.status = MZHIP_STATUS_OUT_FULL;
     if (m.status == 0 && m.out_len) HIP_TRY(mz_d2h(out, d_out, m.out_len));
     if (m.status == 0 && !last) {
         memcpy(state_out, &m.st, sizeof(m.st));
-        HIP_TRY(mz_d2h(model, d_model, ((LZ_NUM_PROBS + 1u) & ~1u) * sizeof(uint16_t)));
+        HIP_TRY(mz_d2h(model, d_model, model_bytes));
     }
-    if (out_len) *out_len = m.out_len;
+    give(out_len, m.out_len);
     return m.status;
 }
 
@@ -1216,9 +1206,6 @@ int32_t mzhip_xz_encode_host(const uint8_t *in, uint32_t in_len, uint8_t *out, u
 // *unpadded receives the block's unpadded size for the index (mzhip_xz_encode_finish_host writes it)
 static int32_t xz_encode_impl(const uint8_t *in, uint32_t in_len, int32_t preset, int part, int first, uint8_t *out, uint32_t out_cap,
                               uint32_t *out_len, uint32_t *crc, uint64_t *unpadded) {
-    DeviceCtx *c = nullptr;
-    int32_t rc = ctx_for_current(&c);
-    if (rc) return rc;
     /* One .xz block = ONE parsed stream (round 4): the block's bytes go through the chain pass and the block parse as a
      * method-14 stream does -- a chunk's matches reach back over the chunks before it, 8 MiB at most -- and every 64 KiB
      * block of the parse becomes one LZMA2 chunk, range-coded by a wave of its own with a fresh coder and model (the first
@@ -1232,37 +1219,34 @@ static int32_t xz_encode_impl(const uint8_t *in, uint32_t in_len, int32_t preset
         uint32_t in_len, out_cap, out_len, crc;
         int32_t status;
         uint32_t crc_init;
-    } m;
-    memset(&m, 0, sizeof(m));
-    const size_t meta_pad = 256;
-    const size_t per_chunk = ((size_t)np * 2 * sizeof(uint32_t) + 63) & ~(size_t)63; /* chunk_len[np], chunk_status[np] */
-    const size_t in_pad = ((size_t)in_len + 63) & ~(size_t)63;
-    const size_t out_bytes = (size_t)np * pcap;
+    };
+    HostCall<Meta> hc;
+    Meta &m = hc.m;
     const size_t tok_words = (size_t)np * MZ_DEF_BLOCK;
-    const size_t scratch_bytes = (tok_words * 2 + ((size_t)1 << MZ_LZE_FAR_HBITS) + np) * sizeof(uint32_t) + 64;
-    Staging sc;
-    rc = sc.get(c, meta_pad + per_chunk + in_pad + ((out_bytes + 63) & ~(size_t)63) + scratch_bytes + 64);
+    const size_t o_chunk = hc.take((size_t)np * 2 * sizeof(uint32_t), 64); /* chunk_len[np], chunk_status[np] */
+    m.in_off = hc.take(in_len, 64);
+    m.out_off = hc.take((size_t)np * pcap, 64);
+    const size_t o_tok = hc.take((tok_words * 2 + ((size_t)1 << MZ_LZE_FAR_HBITS) + np) * sizeof(uint32_t) + 64, 64);
+    m.in_len = in_len;
+    m.out_cap = pcap;
+    int32_t rc = hc.begin();
     if (rc) return rc;
-    uint8_t *base = (uint8_t *)sc.p;
+    DeviceCtx *c = hc.c;
+    uint8_t *base = hc.at(0), *d_out = hc.at(m.out_off);
     std::vector<uint32_t> h_len(np ? np : 1, 0);
     std::vector<int32_t> h_status(np ? np : 1, 0);
     uint32_t total_crc = 0;
-    uint8_t *d_in = base + meta_pad + per_chunk, *d_out = d_in + in_pad;
     if (np) {
-        m.in_off = (uint64_t)(d_in - base);
-        m.out_off = (uint64_t)(d_out - base);
-        m.in_len = in_len;
-        m.out_cap = pcap;
-        HIP_TRY(mz_h2d(base, &m, sizeof(m)));
-        HIP_TRY(mz_h2d(d_in, in, in_len));
-        Meta *dm = (Meta *)base;
+        HIP_TRY(hc.put_meta());
+        HIP_TRY(mz_h2d(hc.at(m.in_off), in, in_len));
+        Meta *dm = hc.dm;
         hipStream_t s = MZ_HOST_STREAM;
         LzmaEncChunksArgs r;
-        rc = lz_parse_one_stream(c, s, r.a, base, dm, np, 0, preset, (uint32_t *)(d_out + ((out_bytes + 63) & ~(size_t)63)));
+        rc = lz_parse_one_stream(c, s, r.a, base, dm, np, 0, preset, (uint32_t *)hc.at(o_tok));
         if (rc) return rc;
         r.nchunks = np;
         r.chunk_cap = pcap;
-        r.chunk_len = (uint32_t *)(base + meta_pad);
+        r.chunk_len = (uint32_t *)hc.at(o_chunk);
         r.chunk_status = (int32_t *)(r.chunk_len + np);
         hipLaunchKernelGGL(k_lzma2_chunks_encode, dim3(resident_grid(np, (uint32_t)c->cu_count * 9u)), dim3(64), 0, s, r); /* 17 KiB LDS per single-wave workgroup */
         {
@@ -1272,8 +1256,7 @@ static int32_t xz_encode_impl(const uint8_t *in, uint32_t in_len, int32_t preset
         /* the block's check: CRC-32 of its uncompressed bytes, where they lie */
         rc = mzhip_crc32_batch(base, &dm->in_off, &dm->in_len, 1, &dm->crc_init, &dm->crc, s);
         if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(mz_d2h(&m, base, sizeof(m)));
+        HIP_TRY(hc.wait_fetch_meta());
         HIP_TRY(mz_d2h(h_len.data(), r.chunk_len, (size_t)np * sizeof(uint32_t)));
         HIP_TRY(mz_d2h(h_status.data(), r.chunk_status, (size_t)np * sizeof(int32_t)));
         total_crc = m.crc;
@@ -1286,18 +1269,11 @@ static int32_t xz_encode_impl(const uint8_t *in, uint32_t in_len, int32_t preset
         pos += n;
         return true;
     };
-    auto le32 = [](uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); };
-    auto vli = [](uint8_t *p, uint64_t v) -> uint32_t {
-        uint32_t k = 0;
-        while (v >= 0x80) { p[k++] = (uint8_t)(v | 0x80); v >>= 7; }
-        p[k++] = (uint8_t)v;
-        return k;
-    };
     uint8_t hdr[12] = {0xFD, '7', 'z', 'X', 'Z', 0x00, 0x00, 0x01 /* check: CRC32 */, 0, 0, 0, 0};
-    le32(hdr + 8, mzhip_crc32_host(0, hdr + 6, 2));
+    put_le32(hdr + 8, mzhip_crc32_host(0, hdr + 6, 2));
     uint8_t bh[12] = {0x02 /* (2 + 1) * 4 bytes */, 0x00 /* one filter, no sizes */, 0x21 /* LZMA2 */, 0x01,
                       (uint8_t)(np > 1u ? 0x16 /* 8 MiB: the reach of the parse's links */ : 0x08 /* 64 KiB */), 0, 0, 0, 0, 0, 0, 0};
-    le32(bh + 8, mzhip_crc32_host(0, bh, 8));
+    put_le32(bh + 8, mzhip_crc32_host(0, bh, 8));
     if ((!part || first) && !put(hdr, 12)) return MZHIP_STATUS_OUT_FULL;
     if (!put(bh, 12)) return MZHIP_STATUS_OUT_FULL;
     const uint32_t data_start = pos;
@@ -1331,34 +1307,18 @@ static int32_t xz_encode_impl(const uint8_t *in, uint32_t in_len, int32_t preset
     const uint32_t csize_blk = pos - data_start;
     if (!put(zero4, (4u - (csize_blk & 3u)) & 3u)) return MZHIP_STATUS_OUT_FULL;
     uint8_t chk[4];
-    le32(chk, total_crc);
+    put_le32(chk, total_crc);
     if (!put(chk, 4)) return MZHIP_STATUS_OUT_FULL;
     if (unpadded) *unpadded = 12ull + csize_blk + 4ull;
-    if (part) {
-        if (out_len) *out_len = pos;
-        if (crc) *crc = total_crc;
-        return 0;
+    if (!part) { /* a whole stream: the index over this one block and the footer */
+        const uint64_t unp = 12ull + csize_blk + 4ull, unc = in_len;
+        uint32_t tail = 0;
+        rc = mzhip_xz_encode_finish_host(&unp, &unc, 1, out + pos, out_cap - pos, &tail);
+        if (rc) return rc;
+        pos += tail;
     }
-    uint8_t idx[32];
-    uint32_t k = 0;
-    idx[k++] = 0x00;
-    idx[k++] = 0x01;
-    k += vli(idx + k, 12ull + csize_blk + 4ull);
-    k += vli(idx + k, in_len);
-    while (k & 3u) idx[k++] = 0;
-    le32(idx + k, mzhip_crc32_host(0, idx, k));
-    k += 4;
-    if (!put(idx, k)) return MZHIP_STATUS_OUT_FULL;
-    uint8_t ft[12];
-    le32(ft + 4, k / 4 - 1);
-    ft[8] = 0x00;
-    ft[9] = 0x01;
-    le32(ft, mzhip_crc32_host(0, ft + 4, 6));
-    ft[10] = 'Y';
-    ft[11] = 'Z';
-    if (!put(ft, 12)) return MZHIP_STATUS_OUT_FULL;
-    if (out_len) *out_len = pos;
-    if (crc) *crc = total_crc;
+    give(out_len, pos);
+    give(crc, total_crc);
     return 0;
 }
 

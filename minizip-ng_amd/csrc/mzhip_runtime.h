@@ -6,7 +6,9 @@
 //   host TUs   mzhip_host.cpp, mzhip_crc_host.cpp, mzhip_prime.cpp (the host C++ compiler, <hip/hip_runtime_api.h> only):
 //              device queries, the per-thread stream pool, staging, the one-entry host calls that only call launchers, the
 //              CRC lane, the RCCL gather, both prime caches.
-// This header declares exactly what crosses between them and names no kernel and no core type.
+// This header declares exactly what crosses between them and names no kernel and no core type.  It also carries what both
+// halves' one-entry host calls are built on, on the runtime API alone: the copies on a stream, Staging, and HostCall -- the
+// context, the staging lease, the carving of the buffer and the meta block's upload and fetch of one such call.
 #ifndef MZHIP_RUNTIME_H
 #define MZHIP_RUNTIME_H
 
@@ -14,6 +16,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/mzhip.h"
 
@@ -82,6 +85,56 @@ static inline hipError_t mz_d2h(void *dst, const void *src, size_t n) {
 struct Staging : ScratchLease {
     int32_t get(DeviceCtx *ctx, size_t bytes) { return ScratchLease::get(ctx_scratch(ctx), bytes, MZ_HOST_STREAM); }
 };
+
+// The round trip of a synchronous one-entry host call, once: the device context, the staging lease, the carving of the
+// buffer and the traffic of the call's meta block (the words a batch of one reads and writes: offsets, lengths, status,
+// states -- whatever the call's `Meta` holds; it lies first in the buffer).  A call states its layout as take() steps before
+// begin() and asks at() for the regions' addresses after it; offsets are from the buffer's first byte, which is what the
+// batch launchers' in_off / out_off count from as well.
+struct StagedCall {
+    DeviceCtx *c = nullptr;
+    size_t take(size_t bytes, size_t align = 16) { // the next region: `bytes` at a multiple of `align` -> its offset
+        const size_t off = (end + align - 1) & ~(align - 1);
+        end = off + bytes;
+        return off;
+    }
+    int32_t begin() { // everything is taken: the context of the current device (unless the call has set `c`) and a staging buffer that holds it all
+        const int32_t rc = c ? 0 : ctx_for_current(&c);
+        return rc ? rc : sc.get(c, end);
+    }
+    uint8_t *at(size_t off) const { return (uint8_t *)sc.p + off; }
+
+  private:
+    Staging sc;
+    size_t end = 0;
+};
+template <class Meta>
+struct HostCall : StagedCall {
+    Meta m;             // the host's copy, zeroed
+    Meta *dm = nullptr; // the device's (after begin)
+    HostCall() {
+        memset(&m, 0, sizeof(m));
+        take(sizeof(Meta), 64);
+    }
+    int32_t begin() {
+        const int32_t rc = StagedCall::begin();
+        dm = (Meta *)at(0);
+        return rc;
+    }
+    hipError_t put_meta() { return mz_h2d(dm, &m, sizeof(m)); }
+    hipError_t fetch_meta() { return mz_d2h(&m, dm, sizeof(m)); } // the copy behind the launches, and the wait for it
+    hipError_t wait_fetch_meta() {                                // the stream's wait of its own first, where a call has always had one
+        const hipError_t e = hipStreamSynchronize(MZ_HOST_STREAM);
+        return e != hipSuccess ? e : fetch_meta();
+    }
+};
+// a result the caller may not have asked for: a null pointer is skipped
+template <class T, class V>
+static inline void give(T *dst, V v) {
+    if (dst) *dst = (T)v;
+}
+// (the .xz container's integers)
+static inline void put_le32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
 
 // ---- defined in mzhip_host.cpp: checksums of the new bytes of a decoded window (the many-wave decoders of the device TU ask them too)
 int32_t window_piece_crcs(uint8_t *base, size_t out_off, uint32_t hist, uint32_t out_len, uint32_t seg_first, uint32_t seg_stride,
