@@ -347,8 +347,10 @@ MZHIP_API int32_t mzhip_deflate_batch_level(const void *d_in, const uint64_t *d_
 /* Replaces, for n streams at once, mz_stream_lzma_write/_close (mz_strm_lzma.c:244-332 -> liblzma
  * lzma_alone_encoder) + mz_crypt_crc32_update (mz_zip.c:2064).  Two kernels: the LZ77 parse (one wave per 64 KiB
  * block of any stream) and the adaptive range coder (one wave per stream -- it is strictly serial).  d_mode (may be
- * NULL = all 0): 0 -> a complete ZIP method-14 payload (4-byte magic, lc3/lp0/pb2 + 64 KiB dictionary, data, end
- * marker: what mz_zip.c expects with MZ_ZIP_FLAG_LZMA_EOS_MARKER); 1 -> the raw payload of one LZMA2 chunk.
+ * NULL = all 0): 0 -> a complete ZIP method-14 payload (4-byte magic, lc3/lp0/pb2 + the dictionary -- 64 KiB for a stream
+ * of one 64 KiB block, mzhip_lzma_encode_history_bytes() beyond: matches reach back 32 KiB in the one, one byte less than
+ * the dictionary in the other --, data, end marker: what mz_zip.c expects with MZ_ZIP_FLAG_LZMA_EOS_MARKER); 1 -> the raw
+ * payload of one LZMA2 chunk.  (tests/test_gpu_lzma_tokens.py measures every distance and every packet of both.)
  * max_in_len = upper bound of d_in_len[] (sizes the token scratch: 4 bytes per input position, stream-ordered
  * allocation).  d_out_cap[i] >= len + len/8 + 1024 always suffices.  The bytes are valid LZMA but not liblzma's:
  * parity is "the reference's mz_stream_lzma_read returns the input".  d_crc = CRC-32 of the INPUT. */

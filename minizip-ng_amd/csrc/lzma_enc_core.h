@@ -11,13 +11,17 @@
  *                    which the DEFLATE encoder shares (hash buckets in LDS, inheritance, lazy rule, greedy selection by
  *                    pointer doubling), around a match measurement of its own (no prefetch, the far links);
  *                    the previous 32 KiB of the stream are hashed first so matches may reach back across the block
- *                    boundary; tokens (literal | length 4..258 + distance <= 32 KiB) go to HBM;
+ *                    boundary, and the chain pass's links (mz_lz_chain) lead further back in a stream of more than one
+ *                    block; tokens (literal | length 4..273 + distance: <= 32 KiB in a stream of one block, below
+ *                    MZ_LZE_FAR_DICT = 8 MiB beyond; no token crosses the end of its block) go to HBM;
  *   mz_lzma_rc_encode one wave per stream: the adaptive range coder is strictly serial, so the token sequence is
  *                    coded by wave-uniform code with the probability model in LDS; 64 tokens at a time are
  *                    prepared in parallel (positions by prefix sum, the literal context byte and the match byte
  *                    fetched from the input by the lanes) so that the serial loop never waits for HBM; output
  *                    bytes are collected in a 256-byte VGPR window and stored coalesced.
- * Properties written: lc 3, lp 0, pb 2, dictionary 64 KiB (every distance is below 32 KiB).
+ * Properties written: lc 3, lp 0, pb 2; dictionary 64 KiB for a stream of one block (every distance is at most 32 KiB),
+ * MZ_LZE_FAR_DICT beyond (every distance is below it).  tests/lzma_tokens.py reads the streams packet by packet and
+ * tests/test_lzma_tokens.py / test_gpu_lzma_tokens.py hold them to all of this.
  */
 #ifndef MZHIP_LZMA_ENC_CORE_H
 #define MZHIP_LZMA_ENC_CORE_H
@@ -43,7 +47,9 @@
 #define MZ_LZE_MAXMATCH 273u /* the longest match LZMA codes (2 + 16 + 255) */
 #define MZ_LZE_CHAIN_WAVES 1024u /* resident waves of the chain pass (1 MiB of table each) */
 #ifndef MZ_LZE_FAR_MINLEN
-#define MZ_LZE_FAR_MINLEN 5u /* a far match shorter than this costs more than the literals it replaces */
+#define MZ_LZE_FAR_MINLEN 5u /* a match further than 32 KiB back and shorter than this costs more than the literals it replaces:
+                                no token is one -- neither a candidate as measured nor one handed on by MZ_LZ_INHERIT, which
+                                arrives a byte or two shorter */
 #endif
 
 #ifndef MZ_LZE_FAR_GAIN
@@ -218,6 +224,10 @@ MZ_DEV uint32_t mz_lz_tokenize(const uint8_t *in, uint32_t blk, uint32_t blk_end
             P(lit) = (uint32_t)in[pos < blk_end ? pos : blk];
         }
         MZ_LZ_INHERIT(pk, nv, ways)
+        MZ_LANES { /* (a position that inherits had no match of its own: it goes back to a literal) */
+            const uint32_t l = P(pk) & 511u;
+            if (l && l < MZ_LZE_FAR_MINLEN && (P(pk) >> 9) > 32768u) P(pk) = 0u;
+        }
         MZ_LZ_LAZY(pk, lit, g1, nv, ways)
 #define MZ_LZ_SELECT_MARK ((void)0) /* (K6 has no section marks) */
 #include "lz77_select.inc"

@@ -521,3 +521,39 @@ def incompressible_cases():
     if "noise" not in _ECHO:
         _ECHO["noise"] = [("noise/%d" % n, np.random.RandomState(7000 + k).bytes(n)) for k, n in enumerate((1, 65535, 65536, 65537, 131071))]
     return _ECHO["noise"]
+
+
+def lzma_echo_cases(far):
+    """[(name, data, period)]: inputs for the LZMA ENCODER (K6), whose matches reach back 32 KiB in a stream of one 64 KiB
+    block and far - 1 bytes (far = its history_bytes()) in a longer one, and whose packets never cross a multiple of 64 KiB.
+    period = (D, second): the bytes from `second` on repeat what lies exactly D back, and nothing else does -- an encoder
+    that may take that echo should, one that may not has literals left -- or None.
+      "near/P"  r + r[:65536 - P], r = P random bytes: one block, the echo at the reach of a one-block stream and one short
+                of it; "near/32769": the far layout below in 36869 bytes, one byte beyond that reach;
+      "far/D"   R + zeros + R + b"tail", R = 4096 random bytes, the second R exactly D back: at and around one block, with
+                the second R across a seam of the parse (2 and 16 blocks, less 2000 and 1999), at 1 MiB, at far - 1 (taken)
+                and at far and far + 1 (not taken).  The filler is zeros so that the chain pass's table stays clean: all-zero
+                positions share one bucket, and R's second copy finds its first directly, whatever the chain depth;
+      structure only: nothing, one byte, runs of 300, 65536 and 65537 bytes, text of 200000 bytes and of one block less one,
+                exactly, plus one, and a block of noise in front of text (the .xz writer stores it).
+    The three far-sized cases are 8.4 MB each.  Built once per process; nobody changes it."""
+    key = ("lzma", far)
+    if key in _ECHO:
+        return _ECHO[key]
+    c = corpus()
+    cases = []
+    for k, p in enumerate((32767, 32768)):
+        r = np.random.RandomState(8100 + k).bytes(p)
+        cases.append(("near/%d" % p, r + r[:65536 - p], (p, p)))
+    R = np.random.RandomState(8200).bytes(4096)
+    far_layout = lambda d: R + bytes(d - 4096) + R + b"tail"
+    cases.append(("near/32769", far_layout(32769), (32769, 32769)))
+    for d in (65536, 65537, 2 * 65536 - 2000, 2 * 65536 - 1999, 16 * 65536 - 2000, 1 << 20, far - 1, far, far + 1):
+        cases.append(("far/%d" % d, far_layout(d), (d, d)))
+    noise = np.random.RandomState(8300).bytes(65536)
+    for name, d in (("empty", b""), ("one", b"a"), ("run/300", b"r" * 300), ("run/65536", b"r" * 65536), ("run/65537", b"r" * 65537),
+                    ("text/200000", c[:200000]), ("text/65535", c[:65535]), ("text/65536", c[:65536]), ("text/65537", c[:65537]),
+                    ("noise+text", noise + c[:1000])):
+        cases.append((name, d, None))
+    _ECHO[key] = cases
+    return cases
