@@ -366,6 +366,47 @@ MZHIP_API int32_t mzhip_lzma_encode_batch_preset(const void *d_in, const uint64_
                                                  const uint32_t *d_out_cap, const uint8_t *d_mode, uint32_t n, int32_t preset,
                                                  uint32_t *d_out_len, uint32_t *d_crc, int32_t *d_status, void *stream);
 
+/* bzip2 encode (ZIP method 12) ---------------------------------------------------------- */
+
+/* Replaces, for n entries at once, mz_stream_bzip_write / _close (mz_strm_bzip.c -> libbz2 BZ2_bzCompressInit(level, 0, 0),
+ * BZ2_bzCompress) + mz_crypt_crc32_update (mz_zip.c:2064).  Entry i's output is ONE bzip2 stream: "BZh" + the block-size
+ * digit, the blocks (first run-length stage, Burrows-Wheeler transform, move-to-front, RUNA / RUNB, 2 .. 6 Huffman tables
+ * of lengths 1 .. 17 chosen per 50 symbols), the end marker and the combined CRC, padded to a byte.  One wave per entry
+ * writes all of its blocks; a block closes when its run-length-coded symbols would exceed 100000 * level - 19.  The bytes
+ * are valid bzip2 but not libbz2's (the tables differ): parity is "BZ2_bzDecompress returns the input".
+ * level: 1 .. 9 the block-size digit, -1 the default 6 (mz_stream_bzip_set_prop_int64); anything else returns
+ * MZ_PARAM_ERROR (-102) and launches nothing.  n == 0 returns 0.  max_in_len = upper bound of d_in_len[]: it sizes the
+ * device scratch, 17 bytes per symbol of min(100000 * level, max_in_len + max_in_len / 4 + 1) per resident wave
+ * (mzhip_bzip2_encode_launch_geometry); an entry longer than it is still written correctly, in smaller blocks.
+ * Memory contract of the other encoders: the input is read at byte granularity, never outside d_in + d_in_off[i] .. +
+ * d_in_len[i], and is not changed; nothing is stored outside d_out + d_out_off[i] .. + d_out_cap[i], nor behind d_out_len[i]
+ * when the status is 0.  d_crc = CRC-32 of the INPUT.
+ * Status: 0; -200 the stream does not fit d_out_cap[i] (d_out_len[i] is 0 then; bytes inside the capacity may have been
+ * written).  d_out_cap[i] >= mzhip_bzip2_encode_bound(d_in_len[i], level) always suffices. */
+MZHIP_API int32_t mzhip_bzip2_encode_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                           uint32_t max_in_len, void *d_out, const uint64_t *d_out_off,
+                                           const uint32_t *d_out_cap, uint32_t n, int32_t level, uint32_t *d_out_len,
+                                           uint32_t *d_crc, int32_t *d_status, void *stream);
+/* An output size that always suffices (0 for a level that is none).  The first run-length stage turns 4 bytes into 5 at the
+ * worst: R = in_len + in_len / 4 symbols in all, in nb <= R / (100000 * level - 24) + 1 blocks (a block that closes holds
+ * at least 100000 * level - 20 symbols; an input of 0 bytes has no block, the bound counts one).  A block of s symbols
+ * codes at most s + 2 symbols (a zero run never takes more symbols than it is long; one to spare, and the end of block), each
+ * with at most 9 bits: no table costs its groups more than the flat code of the alphabet (258 symbols at the most), the
+ * encoder checks that.  Per 50 symbols begun a selector of at most 6 bits.  Per block 105 bits of magic, CRC, flag and
+ * origPtr, 272 of symbol map, 18 of table and selector counts, and six tables of 5 + 258 x 33 bits (a delta-coded length
+ * costs 2 bits per step of at most 16, and one): 51 509 bits.  The stream frame is 14 bytes.  So
+ *   bits = 9 (R + 2 nb) + 6 ((R + 2 nb) / 50 + nb) + 51 509 nb,   bound = 14 + ceil(bits / 8). */
+MZHIP_API uint64_t mzhip_bzip2_encode_bound(uint32_t in_len, int32_t level);
+/* What a mzhip_bzip2_encode_batch launch would use: single-wave workgroups (min(n, resident waves of the device)) and bytes
+ * of device scratch (rotation orders, ranks, symbols and selectors, per wave of the grid); (0, 0) for n == 0 or a level
+ * that is none. */
+MZHIP_API void mzhip_bzip2_encode_launch_geometry(uint32_t n, uint32_t max_in_len, int32_t level, uint32_t *grid,
+                                                  uint64_t *scratch_bytes);
+/* one entry from a host buffer (H2D + kernel + D2H in one staging round trip, synchronous); *crc = CRC-32 of `in`.
+ * Returns the status: 0, -200 (the stream is longer than out_cap; *out_len is 0), -102 (level) */
+MZHIP_API int32_t mzhip_bzip2_encode_host(const uint8_t *in, uint32_t in_len, int32_t level, uint8_t *out, uint32_t out_cap,
+                                          uint32_t *out_len, uint32_t *crc);
+
 /* Host-buffer conveniences (H2D + kernel + D2H, synchronous); these are what the
  * vtbl shims use for one-entry-at-a-time callers (raw DEFLATE: mzhip_inflate_host_a / mzhip_deflate_host_a above / below). */
 MZHIP_API int32_t mzhip_lzma_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, int64_t max_out,

@@ -212,6 +212,45 @@ def bzip2_host(data, out_cap):
     return int(st), int(iu.value), out.raw[: ol.value], int(crc.value)
 
 
+def bzip2_encode_batch(d_in, in_off, in_len, d_out, out_off, out_cap, level=6):
+    """ZIP method 12, the write side: one bzip2 stream per entry through mzhip_bzip2_encode_batch on torch's current stream
+    (asynchronous).  Tensors as for inflate_batch; level 1..9 is the block-size digit, -1 the default 6.  The scratch is
+    sized from the largest in_len (one copy of the lengths to the host).  Returns CUDA tensors (out_len, crc, status);
+    crc is the CRC-32 of the input."""
+    import torch
+
+    require_gpu()
+    n = in_off.numel()
+    dev = d_in.device
+    out_len, crc, status = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    for t, dt in ((in_off, torch.int64), (out_off, torch.int64), (in_len, torch.int32), (out_cap, torch.int32)):
+        assert t.dtype == dt and t.is_cuda and t.is_contiguous()
+    assert d_in.dtype == torch.uint8 and d_out.dtype == torch.uint8
+    max_in_len = int(in_len.max().item()) if n else 0
+    with torch.cuda.device(dev):
+        _check(lib().mzhip_bzip2_encode_batch(d_in.data_ptr(), in_off.data_ptr(), in_len.data_ptr(), max_in_len, d_out.data_ptr(),
+                                              out_off.data_ptr(), out_cap.data_ptr(), n, level, out_len.data_ptr(),
+                                              crc.data_ptr(), status.data_ptr(), _stream_handle()),
+               "mzhip_bzip2_encode_batch")
+    return out_len, crc, status
+
+
+def bzip2_encode_bound(in_len, level=6):
+    """mzhip_bzip2_encode_bound: an output capacity that always suffices (host arithmetic, no device needed)"""
+    return int(lib().mzhip_bzip2_encode_bound(in_len, level))
+
+
+def bzip2_encode_host(data, level=6):
+    """One entry through the host-buffer convenience entry point -> (status, bzip2 stream, crc of the data)."""
+    require_gpu()
+    data = bytes(data)
+    cap = max(bzip2_encode_bound(len(data), level), 1)
+    out = C.create_string_buffer(cap)
+    ol, crc = C.c_uint32(0), C.c_uint32(0)
+    st = lib().mzhip_bzip2_encode_host(data, len(data), level, out, cap, C.byref(ol), C.byref(crc))
+    return int(st), out.raw[: ol.value], int(crc.value)
+
+
 def crc32_host(data, value=0):
     require_gpu()
     return int(lib().mzhip_crc32_host(value, bytes(data), len(data)))

@@ -381,8 +381,8 @@ def crypt_overhead(kind, strength=3):
 
 
 def _check_writer_args(n, method, kind, strength, ae_version):
-    if method not in (0, 8, 14):
-        raise _mz.MzHipError("encode_archive writes methods 0, 8 and 14, not %r" % (method,))
+    if method not in (0, 8, 12, 14):
+        raise _mz.MzHipError("encode_archive writes methods 0, 8, 12 and 14, not %r" % (method,))
     if kind not in (None, "pk", "aes"):
         raise _mz.MzHipError("kind is None, 'pk' or 'aes', not %r" % (kind,))
     if kind == "aes" and (strength not in (1, 2, 3) or ae_version not in (1, 2)):
@@ -397,8 +397,8 @@ def assemble_archive(names, payloads, crcs, usizes, method=8, kind=None, strengt
     mz_zip.c).  crcs / usizes: CRC-32 and length of the plain data.  No data descriptor is written (sizes and CRCs are
     known before any header is), so flag bit 3 stays clear and ZipCrypto's check bytes are the CRC's two high bytes.  AES
     entries are method 99 with the 7-byte 0x9901 field (version, "AE", strength, the real method) in both headers, version
-    needed 51, and -- AE-2 -- CRC 0.  Method 14 sets flag bit 1 (the stream ends in a marker).  Whatever would need ZIP64
-    is refused."""
+    needed 51, and -- AE-2 -- CRC 0.  Method 14 sets flag bit 1 (the stream ends in a marker) and needs version 63, method 12
+    (bzip2) version 46 (mz_zip.c:710-712) and no flag bit of its own.  Whatever would need ZIP64 is refused."""
     import struct
     import time
 
@@ -414,7 +414,7 @@ def assemble_archive(names, payloads, crcs, usizes, method=8, kind=None, strengt
         raw = name.encode("utf-8") if isinstance(name, str) else bytes(name)
         crc, usize = int(crc) & 0xFFFFFFFF, int(usize)
         flag = (1 if kind else 0) | (2 if method == 14 else 0) | (0 if raw.isascii() else 0x800)
-        zmethod, extra, need = method, b"", 63 if method == 14 else 20
+        zmethod, extra, need = method, b"", 63 if method == 14 else 46 if method == 12 else 20
         if kind == "aes":
             extra = struct.pack("<HHH2sBH", MZ_ZIP_EXTENSION_AES, 7, ae_version, b"AE", strength, method)
             zmethod, need = MZ_COMPRESS_METHOD_AES, 51
@@ -440,9 +440,10 @@ def assemble_archive(names, payloads, crcs, usizes, method=8, kind=None, strengt
 
 def encode_archive(entries, method=8, level=6, password=None, kind=None, strength=3, ae_version=2, entropy=os.urandom,
                    device="cuda:0"):
-    """entries: (name, bytes-like) pairs -> the bytes of a ZIP archive, every entry compressed with `method` (0, 8 or 14) at
-    `level` and, with a password, encrypted as `kind` says ("pk" = ZipCrypto, "aes" = WinZip AES of `strength` 1..3, AE-1 or
-    AE-2).  One upload of the data, ONE codec launch (mzhip_deflate_batch_level, mzhip_lzma_encode_batch_preset in mode 0,
+    """entries: (name, bytes-like) pairs -> the bytes of a ZIP archive, every entry compressed with `method` (0, 8, 12 or 14) at
+    `level` (method 12: the block-size digit 1..9, -1 = 6) and, with a password, encrypted as `kind` says ("pk" = ZipCrypto,
+    "aes" = WinZip AES of `strength` 1..3, AE-1 or AE-2).  One upload of the data, ONE codec launch (mzhip_deflate_batch_level,
+    mzhip_bzip2_encode_batch with capacities from mzhip_bzip2_encode_bound, mzhip_lzma_encode_batch_preset in mode 0,
     mzhip_crc32_batch for STORE) whose CRC words are the entries' CRCs, ZipCrypto's check bytes derived from those words on
     the device, 10 n / 16 n bytes drawn from `entropy` (a callable: byte count -> bytes), ONE encrypt call
     (mzhip_pkcrypt_encrypt_batch / mzhip_wzaes_encrypt_batch) straight from the codec's output, one copy back, and
@@ -459,6 +460,10 @@ def encode_archive(entries, method=8, level=6, password=None, kind=None, strengt
     over = crypt_overhead(kind, strength)
     slack = 0 if method == 0 else 64 if method == 8 else 1024          # include/mzhip.h: what always suffices
     cap = usize if method == 0 else usize + usize // 8 + slack
+    if method == 12:
+        if level != -1 and level not in range(1, 10):
+            raise _mz.MzHipError("method 12: level is the block-size digit 1..9 (or -1 = 6), not %r" % (level,))
+        cap = np.array([_mz.bzip2_encode_bound(int(u), level) for u in usize], dtype=np.int64)
     if n and int((cap + over).max()) >= ZIP32_MAX:
         raise _mz.MzHipError("an entry of 4 GiB needs ZIP64, which is not written")
     names = [name for name, _ in entries]
@@ -497,6 +502,10 @@ def encode_archive(entries, method=8, level=6, password=None, kind=None, strengt
                 rc = L.mzhip_deflate_batch_level(d_in.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), d_comp.data_ptr(),
                                                  d_comp_off.data_ptr(), d_cap.data_ptr(), None, n, level, 15, r_len.data_ptr(),
                                                  r_crc.data_ptr(), r_st.data_ptr(), stream)
+            elif method == 12:
+                rc = L.mzhip_bzip2_encode_batch(d_in.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), int(usize.max()),
+                                                d_comp.data_ptr(), d_comp_off.data_ptr(), d_cap.data_ptr(), n, level,
+                                                r_len.data_ptr(), r_crc.data_ptr(), r_st.data_ptr(), stream)
             else:
                 rc = L.mzhip_lzma_encode_batch_preset(d_in.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), int(usize.max()),
                                                       d_comp.data_ptr(), d_comp_off.data_ptr(), d_cap.data_ptr(), None, n, level,

@@ -41,6 +41,7 @@
 #include "lzma_enc_core.h"
 #include "crypt_core.h"
 #include "bzip2_core.h"
+#include "bzip2_enc_core.h"
 
 #ifndef MZ_WAVES_PER_WG
 #define MZ_WAVES_PER_WG 4
@@ -280,6 +281,50 @@ __global__ __launch_bounds__(64) void k_bzip2_batch(Bzip2Args a) {
         // wave-uniform results: stored by all lanes (same address, same value), see MZ_WAVE_FETCH_ADD
         a.out_len[e] = r.out_len;
         a.in_used[e] = r.in_used;
+        a.crc[e] = r.crc;
+        a.status[e] = r.status;
+    }
+}
+
+struct Bzip2EncArgs {
+    const uint8_t *in;
+    const uint64_t *in_off;
+    const uint32_t *in_len;
+    uint8_t *out;
+    const uint64_t *out_off;
+    const uint32_t *out_cap;
+    uint32_t n;
+    uint32_t *out_len;
+    uint32_t *crc;
+    int32_t *status;
+    uint32_t *counter;
+    const mzhip_crc_tables *tabs;
+    uint8_t *scratch;       // scratch_stride bytes per wave of the grid: rotation orders, ranks / symbols, the block, the selectors
+    uint64_t scratch_stride; // MZ_BZE_SCRATCH_BYTES(cap_syms)
+    uint32_t cap_syms;      // MZ_BZE_CAP_SYMS(max_in_len, level)
+    uint32_t level;         // the block-size digit, 1 .. 9
+};
+
+// bzip2 encode (ZIP method 12): one wave per workgroup and per entry (bzip2_enc_core.h), 27.8 KiB of LDS (bit window, the
+// tables' frequencies, lengths and codes, Huffman's queues, MTF list, the two CRC tables), persistent waves over a counter.
+__global__ __launch_bounds__(64) void k_bzip2_encode_batch(Bzip2EncArgs a) {
+    __shared__ __attribute__((aligned(16))) mz_bze_lds lds;
+    __shared__ uint32_t crc_tab[256];
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) crc_tab[i] = a.tabs->byte_tab[i];
+    __syncthreads();
+    MZ_LANE_DECL
+    uint8_t *const scratch = a.scratch + (size_t)blockIdx.x * a.scratch_stride;
+    for (;;) {
+        uint32_t e;
+        MZ_WAVE_FETCH_ADD(e, a.counter);
+        if (e >= a.n) break;
+        mz_bze_result r;
+        const uint64_t io = a.in_off[e], oo = a.out_off[e];
+        const uint8_t *in = a.in + MZ_UNIFORM64(io);
+        uint8_t *out = a.out + MZ_UNIFORM64(oo);
+        mz_bzip2_enc_entry(in, MZ_UNIFORM(a.in_len[e]), out, MZ_UNIFORM(a.out_cap[e]), a.level, a.cap_syms, &lds, crc_tab, a.tabs, scratch, &r);
+        // wave-uniform results: stored by all lanes (same address, same value), see MZ_WAVE_FETCH_ADD
+        a.out_len[e] = r.out_len;
         a.crc[e] = r.crc;
         a.status[e] = r.status;
     }

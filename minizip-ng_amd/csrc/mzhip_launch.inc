@@ -405,6 +405,61 @@ int32_t mzhip_bzip2_batch(const void *d_in, const uint64_t *d_in_off, const uint
     return launched("k_bzip2_batch", hipGetLastError(), sc);
 }
 
+/* bzip2 encode: the sort of a block's rotations needs, per resident wave and per symbol the scratch holds, two rotation
+ * orders and two rank arrays of 4 bytes each (prefix doubling reads one pair and writes the other; the second rank array
+ * is the scatter's fill counts, the first holds the 16-bit symbols once the sort is done) and the symbol itself: 17 bytes,
+ * and 18 048 bytes of selectors.  The scratch holds C = min(100000 * level, max_in_len + max_in_len / 4 + 1) symbols, rounded
+ * up to 64 (MZ_BZE_CAP_SYMS): MZ_BZE_SCRATCH_BYTES(C) = 17 C + 18 048, rounded up to 256 -- 1 411 840 bytes for entries of
+ * 64 KiB at any level (C = 81 984), 15 318 784 for entries of 900 000 bytes and more at level 9 (C = 900 032).
+ * 4 single-wave workgroups per CU, one per SIMD: the sort waits for scattered loads, so more waves would hide more of it
+ * -- LDS (27.8 KiB per wave) would allow 5 -- but every further wave per CU costs 3.9 GB of scratch on a 256-CU device at
+ * level 9; 4 per CU is 15.7 GB for a full grid there and 1.4 GB for 64 KiB entries.  grid = min(n, resident): a small
+ * batch costs a small scratch. */
+#define MZ_BZE_WAVES_PER_CU 4u
+
+static uint32_t bzip2_enc_grid(const DeviceCtx *c, uint32_t n) { return resident_grid(n, (uint32_t)c->cu_count * MZ_BZE_WAVES_PER_CU); }
+
+uint64_t mzhip_bzip2_encode_bound(uint32_t in_len, int32_t level) {
+    const uint64_t digit = MZ_BZE_LEVEL(level);
+    return digit ? MZ_BZE_BOUND(in_len, digit) : 0u;
+}
+
+void mzhip_bzip2_encode_launch_geometry(uint32_t n, uint32_t max_in_len, int32_t level, uint32_t *grid, uint64_t *scratch_bytes) {
+    DeviceCtx *c = nullptr;
+    const uint32_t digit = MZ_BZE_LEVEL(level);
+    uint32_t g = 0;
+    if (digit && ctx_for_current(&c) == 0) g = bzip2_enc_grid(c, n);
+    if (grid) *grid = g;
+    if (scratch_bytes) *scratch_bytes = (uint64_t)g * MZ_BZE_SCRATCH_BYTES(MZ_BZE_CAP_SYMS(max_in_len, digit ? digit : 1u));
+}
+
+int32_t mzhip_bzip2_encode_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, uint32_t max_in_len,
+                                 void *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap, uint32_t n, int32_t level,
+                                 uint32_t *d_out_len, uint32_t *d_crc, int32_t *d_status, void *stream) {
+    const uint32_t digit = MZ_BZE_LEVEL(level);
+    if (!digit) {
+        snprintf(g_err, sizeof(g_err), "mzhip_bzip2_encode_batch: level %d is not 1 .. 9 or -1", (int)level);
+        return -102; /* MZ_PARAM_ERROR */
+    }
+    if (n == 0) return 0;
+    Launch L;
+    int32_t rc = L.begin(stream);
+    if (rc) return rc;
+    Bzip2EncArgs a;
+    set_fields(a, L.c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, nullptr, d_crc, d_status);
+    a.counter = L.head.p;
+    a.level = digit;
+    a.cap_syms = MZ_BZE_CAP_SYMS(max_in_len, digit);
+    a.scratch_stride = MZ_BZE_SCRATCH_BYTES(a.cap_syms);
+    const uint32_t grid = bzip2_enc_grid(L.c, n);
+    ScratchLease sc;
+    rc = sc.get(&L.c->scratch, (size_t)grid * a.scratch_stride, L.s);
+    if (rc) return rc;
+    a.scratch = (uint8_t *)sc.p;
+    hipLaunchKernelGGL(k_bzip2_encode_batch, dim3(grid), dim3(64), 0, L.s, a);
+    return launched("k_bzip2_encode_batch", hipGetLastError(), sc);
+}
+
 int32_t mzhip_sha_batch(const void *d_buf, const uint64_t *d_off, const uint32_t *d_len, uint32_t n, uint32_t algorithm,
                         void *d_digest, void *stream) {
     if (algorithm != 20 && (algorithm < 22 || algorithm > 25)) return MZHIP_STATUS_UNSUPPORTED;
