@@ -112,7 +112,7 @@ extern __device__ unsigned long long mz_prof_buf[32];
 #define MZ_CROOT 7 /* code-length-code table bits (== max)  */
 /* ---- chase window: spans of up to MZ_CHASE_SMAX bits, one per lane; the stream reaches a lane through
  * its own ring of MZ_CRING_DW dwords in LDS (+ 2 that mirror the first two, so dword a, a + 1, a + 2 are one address),
- * topped up 4 dwords at a time every second step from a prefetch register; a step record is two dwords
+ * topped up 4 or 8 dwords at a time once per trip of four steps from prefetch registers; a step record is two dwords
  * (mz_chase_step), four records per 16-byte store, row-major [quad of steps][lane] so that the wave's stores of one quad are
  * 1 KiB contiguous. */
 #ifndef MZ_CHASE_SMAX
@@ -133,6 +133,18 @@ extern __device__ unsigned long long mz_prof_buf[32];
 #define MZ_CRING_RS 19u /* row stride: 16 + 2 mirrored, odd */
 #ifndef MZ_PF_GROUPS
 #define MZ_PF_GROUPS 2 /* groups of four stream dwords a lane loads at a time (inflate_walk.inc): 1 or 2 */
+#endif
+#ifndef MZ_WALK_EDGE_BRANCH
+#define MZ_WALK_EDGE_BRANCH 1 /* the walks' refill loads (inflate_walk.inc): 1 = a group inside the input is one 16-byte load and nothing
+                                 else, the two edge groups of a view sit in a branch of their own; 0 = selects in every lane (round 4 .. 8) */
+#endif
+#ifndef MZ_WALK_TRIP_REFILL
+#define MZ_WALK_TRIP_REFILL 1 /* 1 = one refill check per trip of four steps that hands over up to both prefetched groups, no
+                                 half-selects; 0 = a check every second step, one group per check (round 6 .. 8).  MZ_PF_GROUPS 2 only */
+#endif
+#if MZ_WALK_TRIP_REFILL && MZ_PF_GROUPS != 2
+#undef MZ_WALK_TRIP_REFILL
+#define MZ_WALK_TRIP_REFILL 0
 #endif
 #ifndef MZ_EMIT_GROUP
 #define MZ_EMIT_GROUP 8u /* records one lane turns into bytes per emit round (4 or 8: records are stored in quads) */

@@ -53,8 +53,10 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
      * inside the input is one 16-byte load.  Only three kinds do not: the group of dword 0 when in[] does not start on a
      * dword boundary, the group that holds the last (partial) dword, and everything behind it (zeros).  The first two are
      * eight wave-uniform values (`ev`, lanes 0 .. 7: MZ_EDGE_GROUPS of mz_inflate_entry loads them once per view; scalar
-     * registers here), masked as mz_load_stream_dword masks them: a refill is ONE global load
-     * for every lane -- from a harmless interior address where the group is an edge -- and eight selects.  (The r3 refill
+     * registers here), masked as mz_load_stream_dword masks them.  MZ_CHASE_LOAD_DW4, the initial fill of a ring in front
+     * of the loops, is ONE global load for every lane -- from a harmless interior address where the group is an edge --
+     * and eight selects; the refills inside the two loops go through MZ_CHASE_RELOAD_DW4 below, which was the same until
+     * round 9 and is a plain load with the edges in a branch since.  (The r3 refill
      * carried four masked loads with 64-bit address arithmetic, ~100 instructions and a dozen registers, through both walk
      * loops; a copy of the edge groups in LDS turns the load into a flat one -- a select between a global and an LDS
      * pointer -- and a copy in global scratch costs every window a store, a fence and a round trip before its first load:
@@ -78,6 +80,39 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         P(dst)[(o_) + 2] = int_ ? v_.v[2] : z_ ? e0[2] : l_ ? el[2] : 0u;                    \
         P(dst)[(o_) + 3] = int_ ? v_.v[3] : z_ ? e0[3] : l_ ? el[3] : 0u;                    \
     }
+    /* The same for the refills inside the two walk loops, where the selects above were ~50 of the ~70 vector instructions of
+     * a check that runs in every wave at every check, for two groups per view that almost no lane ever loads
+     * (MZ_WALK_EDGE_BRANCH 1).  A lane whose group lies inside the input does its one 16-byte load and nothing else; a lane
+     * whose group does not loads nothing -- no byte outside the aligned dwords of [in, in + in_len) is touched, and none
+     * from a stand-in address either -- and takes its values from `el` or zeros in a branch of its own, which the wave
+     * jumps over when no lane is there.
+     *   The group of dword 0 cannot occur here: a lane starts with hi = (first dword & ~3) + MZ_CRING_DW >= 16, hi only
+     * grows, and a refill loads the groups at hi and hi + 4 >= 16.  So every d_ is above dw_lo (which is 0 or 1), `e0` is
+     * never looked at, and "inside the input" is d_ + 4 <= dw_hi alone.  What is left of the edges: d_ == gl4, the
+     * group with the last (partial) dword, already masked in `el`; and d_ > gl4, zeros.  (gl4 + 4 > dw_hi always, so the
+     * three cases do not overlap.) */
+#if MZ_WALK_EDGE_BRANCH
+#define MZ_CHASE_RELOAD_DW4(dst, o_, d_)                                                     \
+    {                                                                                        \
+        const uint32_t dd_ = (d_); /* a multiple of 4, >= MZ_CRING_DW */                     \
+        if (dd_ + 4u <= dw_hi) {                                                             \
+            mz_dw4 v_;                                                                       \
+            __builtin_memcpy(&v_, in_al + (dd_ << 2), 16);                                   \
+            P(dst)[(o_) + 0] = v_.v[0];                                                      \
+            P(dst)[(o_) + 1] = v_.v[1];                                                      \
+            P(dst)[(o_) + 2] = v_.v[2];                                                      \
+            P(dst)[(o_) + 3] = v_.v[3];                                                      \
+        } else {                                                                             \
+            const uint32_t l_ = (dd_ == gl4) ? 1u : 0u;                                      \
+            P(dst)[(o_) + 0] = l_ ? el[0] : 0u;                                              \
+            P(dst)[(o_) + 1] = l_ ? el[1] : 0u;                                              \
+            P(dst)[(o_) + 2] = l_ ? el[2] : 0u;                                              \
+            P(dst)[(o_) + 3] = l_ ? el[3] : 0u;                                              \
+        }                                                                                    \
+    }
+#else
+#define MZ_CHASE_RELOAD_DW4(dst, o_, d_) MZ_CHASE_LOAD_DW4(dst, o_, d_)
+#endif
 
     PV(uint32_t, lim); /* where its span ends */
     PV(uint32_t, hi);  /* next stream dword the ring takes ... */
@@ -87,7 +122,7 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
      * round 5: refills + records were 46 % of K1's fabric reads).  MZ_PF_GROUPS = 2: the NEXT TWO groups are loaded together,
      * two 16-byte loads of one instruction pair into the same line, every second refill: half the line fetches for four
      * selects per refill (profiles/r6/ab_k1_pf.log). */
-    PV2(uint32_t, pf, 4 * MZ_PF_GROUPS); /* dwords hi .. hi + 3 (and hi + 4 .. hi + 7), loaded two steps ago or earlier */
+    PV2(uint32_t, pf, 4 * MZ_PF_GROUPS); /* dwords hi .. hi + 3 (and hi + 4 .. hi + 7), loaded at an earlier check */
 #if MZ_PF_GROUPS == 2
     PV(uint32_t, ph); /* which half of pf is next */
 #endif
@@ -134,12 +169,68 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
     }
     MZ_WAVE_SYNC();
 
+#if MZ_WALK_TRIP_REFILL
+    /* ONE refill check per trip of four steps (MZ_WALK_TRIP_REFILL 1; MZ_CRING_DW is 16).  Write c = u >> 5 for the dword
+     * the cursor stands in and gap = hi - c for the dwords of the ring from there on (the ring holds dwords hi - 16 .. hi - 1).
+     * The four slots at hs hold dwords hi - 16 .. hi - 13: dead when c >= hi - 12, gap <= 12; the four behind them too when
+     * gap <= 8.  The check hands over
+     *     both prefetched groups   when gap <= 8 and both are there (ph == 0),     gap' = gap + 8,
+     *     one                      when gap <= 12 otherwise,                       gap' = gap + 4,
+     *     none                     when gap >= 13,                                 gap' = gap.
+     * INVARIANT: gap' >= 9 after any check, given gap >= 1 before it.
+     *   (a) ph == 0: gap in 1 .. 8 gives gap' = gap + 8 >= 9; gap in 9 .. 12 gives gap' >= 13; gap >= 13 stays.
+     *   (b) ph == 1 (one group handed over, the other still in pf): that state is entered by the middle line above, with
+     *       gap' >= 13, and left by the first check that hands anything over.  Checks in between change nothing, so the
+     *       trip before this check began with gap' >= 13, and a trip moves c by at most 8 (below): gap >= 5 here, and
+     *       gap in 5 .. 12 gives gap' = gap + 4 >= 9; gap >= 13 stays.
+     *   A trip is four steps of at most 63 bits: u grows by at most 252, so c by at most (31 + 252) >> 5 = 8, and
+     *   gap >= 9 - 8 = 1 before the next check: the premise.  A step looks at dwords c, c + 1, c + 2 where it STARTS; the
+     *   trip's last step starts at most 189 bits in, c has moved by at most (31 + 189) >> 5 = 6, and c + 6 + 2 < c + 9 <= hi:
+     *   every dword a step looks at is in the ring (none older than hi - 16 either: gap' <= 16 because nothing is handed
+     *   over above gap 12 and two groups only up to gap 8).  The bound is tight, so the ring cannot be smaller.
+     * pf[0 .. 3] is always the next group: when one group goes, the other moves down (four copies in that branch only,
+     * where round 6 .. 8 picked a half with eight selects at every check), and the two groups of a line are still asked
+     * for together, when both have gone. */
+/* (Reloading the prefetch registers in every lane at every check -- no merge copies, 13 vector instructions fewer per trip --
+ * measured 5 % slower on 64 KiB entries: profiles/r5/call21_probe.log, call22) */
+#define MZ_CHASE_REFILL_PUT(o_)                                                              \
+    {                                                                                        \
+        uint32_t *const w_ = P(row) + P(hs);                                                 \
+        w_[0] = P(pf)[(o_) + 0];                                                             \
+        w_[1] = P(pf)[(o_) + 1];                                                             \
+        w_[2] = P(pf)[(o_) + 2];                                                             \
+        w_[3] = P(pf)[(o_) + 3];                                                             \
+        if (P(hs) == 0u) {                                                                   \
+            P(row)[MZ_CRING_DW] = P(pf)[(o_) + 0];                                           \
+            P(row)[MZ_CRING_DW + 1u] = P(pf)[(o_) + 1];                                      \
+        }                                                                                    \
+        P(hs) = (P(hs) + 4u) & (MZ_CRING_DW - 1u);                                           \
+        P(hi) += 4u;                                                                         \
+    }
+#define MZ_CHASE_REFILL(active_)                                                             \
+    if (active_) {                                                                           \
+        const uint32_t gap_ = P(hi) - (P(u) >> 5);                                           \
+        if (gap_ <= MZ_CRING_DW - 4u) {                                                      \
+            const uint32_t two_ = (gap_ <= MZ_CRING_DW - 8u && P(ph) == 0u) ? 1u : 0u;       \
+            MZ_CHASE_REFILL_PUT(0)                                                           \
+            if (two_) MZ_CHASE_REFILL_PUT(4)                                                 \
+            if (two_ | P(ph)) { /* both are in the ring: the next two groups, one line */    \
+                P(ph) = 0u;                                                                  \
+                MZ_CHASE_RELOAD_DW4(pf, 0, P(hi))                                            \
+                MZ_CHASE_RELOAD_DW4(pf, 4, P(hi) + 4u)                                       \
+            } else {                                                                         \
+                P(pf)[0] = P(pf)[4];                                                         \
+                P(pf)[1] = P(pf)[5];                                                         \
+                P(pf)[2] = P(pf)[6];                                                         \
+                P(pf)[3] = P(pf)[7];                                                         \
+                P(ph) = 1u;                                                                  \
+            }                                                                                \
+        }                                                                                    \
+    }
+#elif MZ_PF_GROUPS == 2
     /* the ring takes the prefetched dwords as soon as their slots are dead (they hold dwords hi - 16 .. hi - 13: the cursor
      * has passed them when it is within 12 dwords of hi); two steps eat at most 126 bits, so checking every second step
      * keeps nine dwords ahead of any cursor, and a step looks at three */
-/* (Reloading the prefetch registers in every lane at every check -- no merge copies, 13 vector instructions fewer per trip --
- * measured 5 % slower on 64 KiB entries: profiles/r5/call21_probe.log, call22) */
-#if MZ_PF_GROUPS == 2
 #define MZ_CHASE_REFILL(active_)                                                             \
     if (active_) {                                                                           \
         if (P(hi) - (P(u) >> 5) <= MZ_CRING_DW - 4u) {                                       \
@@ -158,8 +249,8 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
             P(hi) += 4u;                                                                     \
             P(ph) = s_ ^ 1u;                                                                 \
             if (s_) { /* both halves are in the ring: the next two groups, one line */       \
-                MZ_CHASE_LOAD_DW4(pf, 0, P(hi))                                              \
-                MZ_CHASE_LOAD_DW4(pf, 4, P(hi) + 4u)                                         \
+                MZ_CHASE_RELOAD_DW4(pf, 0, P(hi))                                              \
+                MZ_CHASE_RELOAD_DW4(pf, 4, P(hi) + 4u)                                         \
             }                                                                                \
         }                                                                                    \
     }
@@ -178,7 +269,7 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
             }                                                                                \
             P(hs) = (P(hs) + 4u) & (MZ_CRING_DW - 1u);                                       \
             P(hi) += 4u;                                                                     \
-            MZ_CHASE_LOAD_DW4(pf, 0, P(hi))                                                  \
+            MZ_CHASE_RELOAD_DW4(pf, 0, P(hi))                                                  \
         }                                                                                    \
     }
 #endif
@@ -211,13 +302,19 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         P(sfl) = kk_; /* the last step's K byte: how the walk ended is read off it behind the loop */ \
         P(run) = (((kk_ - 1u) < 0x7Fu) & (nu_ < P(lim))) ? 1u : 0u;                          \
     }
-    /* two steps behind a refill check; the first pair of a trip also sends the quad of the trip before (issued with the \
+    /* two steps (behind a refill check of their own where MZ_WALK_TRIP_REFILL is 0); the first pair of a trip also sends the quad of the trip before (issued with the \
      * loads, waited for with them) */
+#if MZ_WALK_TRIP_REFILL
+#define MZ_CHASE_OWN_PAIR(B) /* (the trip's one check stands at its top) */                  \
+    MZ_LANES { MZ_CHASE_OWN_STEP(B) }                                                        \
+    MZ_LANES { MZ_CHASE_OWN_STEP((B) + 1) }
+#else
 #define MZ_CHASE_OWN_PAIR(B)                                                                 \
     MZ_LANES { MZ_CHASE_REFILL(P(run)) }                                                     \
     MZ_WAVE_SYNC();                                                                          \
     MZ_LANES { MZ_CHASE_OWN_STEP(B) }                                                        \
     MZ_LANES { MZ_CHASE_OWN_STEP((B) + 1) }
+#endif
 #define MZ_CHASE_STORE_LEN(base_, cap_, row_)                                                \
     {                                                                                        \
         mz_dw4 v_;                                                                           \
@@ -409,8 +506,10 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         MZ_WAVE_SYNC();
         MZ_LANES { MZ_CHASE_STEP(0) }
         MZ_LANES { MZ_CHASE_STEP(1) }
+#if !MZ_WALK_TRIP_REFILL
         MZ_LANES { MZ_CHASE_REFILL(P(chs)) }
         MZ_WAVE_SYNC();
+#endif
         MZ_LANES { MZ_CHASE_STEP(2) }
         MZ_LANES { MZ_CHASE_STEP(3) }
         t2 += 4u;
@@ -427,6 +526,9 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
     MZ_CHASE_FENCE();
     MZ_PROF_MARK(5); /* pass 2 */
 #undef MZ_CHASE_REFILL
+#if MZ_WALK_TRIP_REFILL
+#undef MZ_CHASE_REFILL_PUT
+#endif
 #undef MZ_CHASE_OWN_STEP
 #undef MZ_CHASE_OWN_PAIR
 #undef MZ_CHASE_STORE_LEN
@@ -439,6 +541,7 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
 #undef MZ_CHASE_LOAD_LEN
 #undef MZ_CHASE_TARGET
 #undef MZ_CHASE_LOAD_DW4
+#undef MZ_CHASE_RELOAD_DW4
 
     mz_walk_result wr;
     MZ_LANES {
