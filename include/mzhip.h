@@ -470,8 +470,10 @@ MZHIP_API int32_t mzhip_lzma_resume_host(const uint8_t *in, uint32_t in_len, uin
  * receives the window.  `state` is twenty words: flags (in: 1 the model is in `model`, else a fresh block whose first chunk
  * resets everything; 2 the input given is the entry's last; 4 / 8 the next chunk must bring properties / reset the
  * dictionary -- a fresh block is 4 | 8 --; 32 / 64 inside an uncompressed / LZMA chunk.  out: the same bits, 1 = the
- * decoder stopped where it can go on from, 16 = the block's end byte has been consumed, 128 = a data error was met between
- * chunks rather than inside a packet), the range coder, LZMA state and
+ * decoder stopped where it can go on from, 16 = the block's end byte has been consumed, 128 = a data error was met, or the
+ * input ran out (MZHIP_STATUS_BUF_ERROR), between chunks rather than inside a packet, 256 = the input ran out in the
+ * normalisation in front of a packet; after a call that broke off inside an LZMA chunk the two chunk fields say what that
+ * chunk still owed), the range coder, LZMA state and
  * repeat distances, the properties, the block header's dictionary size, out_pos / in_pos as in mzhip_lzma_state, where the
  * dictionary begins in buf (the caller subtracts what it drops, stopping at 0), what is left of a chunk in progress, and
  * the block's check (id 0 none / 1 CRC-32 / 4 CRC-64; value of the block's bytes so far, 0 at the start of a block).  The

@@ -84,6 +84,8 @@ typedef struct mz_lzma_state {
 
 /* the packet loop's stop test: nothing in the one-shot builds */
 #define LZ_RESUME_CHECK() ((void)0)
+/* hook behind a packet's first decision (the only input byte it can have read is the one its normalisation shifts in) */
+#define LZ_FIRST_BIT_DONE() ((void)0)
 /* the wave's issue priority (s_setprio): the chain of decisions against the work all lanes do between packets (CRC tiles,
  * match copies).  MZ_LZPRIO = chain << 2 | bulk; 0 = no priorities, the default: what pays in K1 and K4 loses here -- one
  * round of 4096 x 1 MiB streams 431 ms without, 440 with the chain on top (3 | 0, 2 | 1), 448 with the bulk work on top: every
@@ -488,6 +490,7 @@ MZ_DEV uint32_t mz_prob_half(uint32_t pair, uint32_t b) { return (pair >> (b << 
         const uint32_t ps = opos & pb_mask;                                                                           \
         uint32_t bit;                                                                                                 \
         LZ_BIT(bit, LZ_IS_MATCH + state * 16 + ps);                                                                   \
+        LZ_FIRST_BIT_DONE();                                                                                          \
         if (!bit) {                                                                                                   \
             /* literal */                                                                                             \
             uint32_t sym = 1;                                                                                         \

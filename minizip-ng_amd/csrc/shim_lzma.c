@@ -92,6 +92,12 @@ typedef struct mzhip_lzma_s {
     int8_t xz_err_eager;   /* s_err was met on that walk */
     int8_t xz_tail_tried;  /* TOTAL_OUT_MAX reached, a later read() has walked the rest of the container */
     int64_t xz_tin_hold;   /* >= 0: TOTAL_IN to report while the walk waits for the next staging buffer */
+    int64_t xz_bound_dmax; /* >= 0: s_err is a declared size that ran out inside the block; liblzma decodes on to here in the failing call */
+    /* ... and method 95 in one buffer, a container the device refused: where in the output liblzma refuses it (xz_locate_refusal) */
+    int8_t xz_located;     /* the two below are set */
+    int8_t xz_fail_bound;  /* a declared size ran out inside the block: liblzma decodes on to the block's end in the call it fails */
+    int8_t xz_fail_eager;  /* met on that walk, or on the way into a block: it fails the read() that makes byte xz_fail_p - 1 */
+    int64_t xz_fail_p;     /* output position of the refusal: otherwise it fails the read() that would make byte xz_fail_p */
     /* write side, method 14, entries larger than one segment: coded segment by segment (mzhip_lzma_encode_resume_host), wbuf[]
      * then holds [the previous segment's last 64 KiB | bytes not coded yet] */
     int32_t w_segments;    /* segments coded so far */
@@ -162,6 +168,9 @@ int32_t mz_stream_lzma_open(void *stream, const char *path, int32_t mode) {
     z->hist = z->out_abs = z->in_dropped = z->dict_keep = 0;
     z->xz_phase = z->xz_no_stream = z->xz_err_eager = z->xz_tail_tried = 0;
     z->xz_tin_hold = -1;
+    z->xz_located = z->xz_fail_eager = z->xz_fail_bound = 0;
+    z->xz_bound_dmax = -1;
+    z->xz_fail_p = 0;
     free(z->model);
     z->model = NULL;
     z->w_segments = 0;
@@ -456,7 +465,7 @@ static int xz_vli(const uint8_t *b, int64_t *p, int64_t lim, uint64_t *v) {
     return 1;
 }
 /* a block header of hsize bytes at b (3.1): 0 = LZMA2 alone and well-formed, 1 = anything else */
-static int xz_block_header(const uint8_t *b, int64_t hsize, uint64_t *want_c, uint64_t *want_u, uint32_t *dict) {
+static int xz_block_header(const uint8_t *b, int64_t hsize, uint32_t check_size, uint64_t *want_c, uint64_t *want_u, uint32_t *dict) {
     if (mzhip_crc32_host(0, b, (size_t)(hsize - 4)) != xz_le32(b + hsize - 4))
         return 1;
     const uint8_t fl = b[1];
@@ -467,6 +476,8 @@ static int xz_block_header(const uint8_t *b, int64_t hsize, uint64_t *want_c, ui
     *want_c = *want_u = ~0ull;
     if ((fl & 0x40) && (xz_vli(b, &p, hend, want_c) != 1 || *want_c == 0))
         return 1;
+    if ((fl & 0x40) && *want_c > 0x7FFFFFFFFFFFFFFCull - (uint64_t)hsize - check_size)
+        return 1; /* header + data + check would not fit a VLI: lzma_block_unpadded_size() == 0, refused with the header */
     if ((fl & 0x80) && xz_vli(b, &p, hend, want_u) != 1)
         return 1;
     uint64_t id = 0, psize = 0;
@@ -480,6 +491,26 @@ static int xz_block_header(const uint8_t *b, int64_t hsize, uint64_t *want_c, ui
         if (b[p] != 0)
             return 1;
     return 0;
+}
+/* bytes the LZMA2 chunks from b[from] on decode to, by their headers, up to the block's end byte or the end of b[] */
+static int64_t xz_usize_ahead(const uint8_t *b, int64_t from, int64_t len) {
+    int64_t u = 0;
+    while (from >= 0 && from < len && b[from] != 0) {
+        const uint32_t ctl = b[from];
+        if (ctl >= 0x80) {
+            if (from + 5 > len)
+                break;
+            u += ((int64_t)(ctl & 0x1Fu) << 16) + ((int64_t)b[from + 1] << 8) + b[from + 2] + 1;
+            from += (ctl >= 0xC0 ? 6 : 5) + ((int64_t)b[from + 3] << 8) + b[from + 4] + 1;
+        } else {
+            if (ctl > 2 || from + 3 > len)
+                break;
+            const int64_t n = ((int64_t)b[from + 1] << 8) + b[from + 2] + 1;
+            u += n;
+            from += 3 + n;
+        }
+    }
+    return u;
 }
 static void xz_consume(mzhip_lzma *z, int64_t n) {
     memmove(z->in, z->in + n, (size_t)(z->in_len - n));
@@ -517,7 +548,7 @@ static int32_t xz_stream_start(mzhip_lzma *z) {
     }
     uint64_t wc, wu;
     uint32_t dict32 = 0;
-    if (xz_block_header(z->in + 12, hsize, &wc, &wu, &dict32) != 0)
+    if (xz_block_header(z->in + 12, hsize, z->in[7] == 0 ? 0u : z->in[7] == 1 ? 4u : 8u, &wc, &wu, &dict32) != 0)
         return 0;
     uint64_t dict = dict32 < 4096 ? 4096 : dict32;
     /* (no match reaches back further than the entry is long: see lz_stream_start) */
@@ -617,7 +648,7 @@ static int32_t xz_stream_next(mzhip_lzma *z) {
             const int64_t hsize = ((int64_t)z->in[0] + 1) * 4;
             XZ_WANT(hsize);
             uint32_t dict32 = 0;
-            if (xz_block_header(z->in, hsize, &z->xz_want_csize, &z->xz_want_usize, &dict32) != 0)
+            if (xz_block_header(z->in, hsize, check_size, &z->xz_want_csize, &z->xz_want_usize, &dict32) != 0)
                 XZ_BAD(); /* (a block with filters behind one without: not read in windows) */
             {
                 /* a block with a larger dictionary than the buffer was sized for: the buffer grows (bytes still to be
@@ -659,6 +690,14 @@ static int32_t xz_stream_next(mzhip_lzma *z) {
             a.size = (uint32_t)sizeof(a);
             a.in = z->in;
             a.in_len = (uint32_t)(z->in_len > 0x7FFFFFF0 ? 0x7FFFFFF0 : z->in_len);
+            /* a declared Compressed Size bounds the block while it is decoded (liblzma's block_decoder.c): the chunks get no
+             * byte behind it, and running out of input there is the refusal */
+            int capped = 0;
+            if (z->xz_want_csize != ~0ull && z->xz_want_csize - z->xz_blk_csize <= (uint64_t)a.in_len) {
+                a.in_len = (uint32_t)(z->xz_want_csize - z->xz_blk_csize);
+                sin.flags |= 2u;
+                capped = 1;
+            }
             a.buf = z->out;
             a.buf_cap = (uint32_t)room;
             a.state_in = &sin;
@@ -677,8 +716,45 @@ static int32_t xz_stream_next(mzhip_lzma *z) {
             if (ol < (uint32_t)z->out_len || ol > (uint32_t)room)
                 ol = (uint32_t)z->out_len;
             const int64_t fresh = (int64_t)ol - z->out_len;
+            const int first_chunk = z->xz_blk_usize == 0 && fresh == 0; /* nothing of this block has been decoded */
             z->xz_blk_usize += (uint64_t)fresh;
             z->out_len = ol;
+            {
+                /* what the block still decodes to behind this window, by its chunk headers: liblzma decodes on into the
+                 * caller's buffer in the call it refuses a size in, and counts that in TOTAL_OUT */
+                int64_t rest = 0;
+                if (st != 0) {
+                    int64_t own = (int64_t)sout.chunk_usize_left, at = (int64_t)iu; /* of the chunk it stands in; where the next one starts */
+                    if (sout.flags & 32u)
+                        at += own; /* an uncompressed chunk */
+                    else if ((sout.flags & 1u) && !(sout.flags & 64u))
+                        own = 0; /* in front of a chunk header */
+                    else
+                        at += (int64_t)sout.chunk_csize_left; /* an LZMA chunk: stopped in it, or broke off in it */
+                    rest = own + xz_usize_ahead(z->in, at, z->in_len);
+                }
+                if (z->xz_want_usize != ~0ull && z->xz_blk_usize > z->xz_want_usize) {
+                    /* more than the declared Uncompressed Size: the call that makes the first byte too many fails */
+                    const int64_t excess = (int64_t)(z->xz_blk_usize - z->xz_want_usize);
+                    z->xz_bound_dmax = z->out_abs + z->out_len + rest;
+                    z->out_len -= excess;
+                    z->s_err = MZHIP_STATUS_DATA_ERROR;
+                    z->dev_in_used = 0;
+                    return MZH_OK;
+                }
+                if (capped && st == MZHIP_STATUS_BUF_ERROR) {
+                    /* the declared Compressed Size ran out: between chunks -- but not in front of the block's first, which
+                     * liblzma does not start on without room in the output -- or in the normalisation in front of a packet
+                     * (liblzma normalises when the caller's buffer is full) it fails the call that made the bytes in front,
+                     * inside a packet or an uncompressed chunk the call that would make the next byte */
+                    z->s_err = MZHIP_STATUS_DATA_ERROR;
+                    z->dev_in_used = 0;
+                    if (((sout.flags & 128u) && !first_chunk) || (sout.flags & 256u))
+                        z->xz_err_eager = 1;
+                    z->xz_bound_dmax = z->out_abs + z->out_len + rest;
+                    return MZH_OK;
+                }
+            }
             if (st == 0 || (sout.flags & 1u)) { /* the consumed bytes are done with (a failed call keeps them: TOTAL_IN wants them) */
                 xz_consume(z, iu);
                 z->xz_blk_csize += iu;
@@ -795,7 +871,18 @@ static int32_t lz_stream_fail(mzhip_lzma *z) {
     return MZH_DATA_ERROR;
 }
 
+static int32_t lz_stream_read_(mzhip_lzma *z, void *buf, int32_t size);
 static int32_t lz_stream_read(mzhip_lzma *z, void *buf, int32_t size) {
+    const int64_t before = z->total_out;
+    const int32_t r = lz_stream_read_(z, buf, size);
+    if (r < 0 && z->streaming == 2 && z->xz_bound_dmax >= 0 && z->s_err == MZHIP_STATUS_DATA_ERROR) {
+        z->total_out = before + size < z->xz_bound_dmax ? before + size : z->xz_bound_dmax;
+        if (z->max_total_out >= 0 && z->total_out > z->max_total_out)
+            z->total_out = z->max_total_out;
+    }
+    return r;
+}
+static int32_t lz_stream_read_(mzhip_lzma *z, void *buf, int32_t size) {
     int32_t got = 0;
     while (got < size) {
         int64_t avail = z->out_len - z->out_served;
@@ -885,6 +972,199 @@ static int32_t lz_stream_read(mzhip_lzma *z, void *buf, int32_t size) {
     return got;
 }
 
+/* ---- method 95 in one buffer: in which read() a refused container is refused -------------------------------------------
+ * The device decodes the whole entry and names the first thing wrong in ITS order: a block's size fields are compared when
+ * the block has ended.  liblzma 5.2.5 streams (block_decoder.c, stream_decoder.c), and what the caller sees differs:
+ *   - a block header it refuses (CRC, reserved bits, filters, a Compressed Size with which the block cannot fit a VLI:
+ *     lzma_block_header_decode) fails before a byte of the block is handed out;
+ *   - the declared sizes bound the block WHILE it is decoded: the lzma_code() call in which the LZMA2 decoder has taken more
+ *     input than Compressed Size, or made more output than Uncompressed Size, fails;
+ *   - with a block's last bytes made, the same lzma_code() call walks on through the size comparison, block padding, check,
+ *     the next block header, index and footer as far as the staged input reaches (MZH_STAGING_BYTES at a time,
+ *     mz_strm_lzma.c:170-210): what is wrong there fails the read() that would have returned those last bytes.
+ * So the container is walked once more here, by the LZMA2 chunk headers alone (they carry both sizes), and the refusal is
+ * placed in the output: xz_fail_p, and whether it belongs to the call that makes byte xz_fail_p - 1 (eager) or to the one that
+ * would make byte xz_fail_p.  Where the Compressed Size runs out inside an LZMA chunk, the output position is what the device
+ * decodes of the entry cut there (the coder stops in front of the packet that needs the missing byte, as liblzma's does). */
+static void xz_locate_refusal(mzhip_lzma *z) {
+    const uint8_t *in = z->in;
+    const int64_t n = z->in_len, D = z->out_len, E = z->dev_in_used;
+    int64_t fail_p = D, extent = 0, walked = 0; /* walked: stream position behind the bytes the call in question has made */
+    int eager = 0;
+    z->xz_located = 1;
+    z->xz_fail_p = D;
+    z->xz_fail_eager = 0;
+    if (n < 13)
+        return;
+    const uint32_t check = in[7] & 15u;
+    const int64_t check_size = check == 0 ? 0 : check < 4 ? 4 : check < 7 ? 8 : check < 10 ? 16 : check < 13 ? 32 : 64;
+    int64_t pos = 12, opos = 0;
+    for (;;) {
+        if (pos >= n)
+            return;
+        if (in[pos] == 0 || E < pos) { /* the index, the footer (or a position the walk cannot explain: as the device says) */
+            if (E < pos)
+                return;
+            eager = 1;
+            extent = E + 1;
+            break;
+        }
+        const int64_t hpos = pos, hsize = ((int64_t)in[pos] + 1) * 4;
+        if (hpos + hsize > n)
+            return;
+        if (E < hpos + hsize) { /* the device refused this header */
+            fail_p = opos;
+            eager = 1;
+            extent = hpos + hsize;
+            break;
+        }
+        uint64_t want_c = ~0ull, want_u = ~0ull;
+        uint32_t dict32 = 4096;
+        {
+            int64_t p = 2;
+            if ((in[hpos + 1] & 0x40) && xz_vli(in + hpos, &p, hsize - 4, &want_c) != 1)
+                return;
+            if ((in[hpos + 1] & 0x80) && xz_vli(in + hpos, &p, hsize - 4, &want_u) != 1)
+                return;
+            if (!(in[hpos + 1] & 3) && p + 2 < hsize - 4 && in[hpos + p + 2] <= 40) { /* LZMA2 alone: {0x21, 1, dictionary byte} */
+                const uint32_t db = in[hpos + p + 2];
+                dict32 = db == 40 ? 0xFFFFFFFFu : (uint32_t)(2u | (db & 1u)) << (db / 2u + 11u);
+            }
+        }
+        if (want_c != ~0ull && want_c > (0x7FFFFFFFFFFFFFFCull - (uint64_t)hsize - (uint64_t)check_size)) {
+            fail_p = opos;
+            eager = 1; /* lzma_block_unpadded_size() == 0: refused with the header */
+            extent = hpos + hsize;
+            break;
+        }
+        /* the block's chunks; the first bound liblzma runs into */
+        const int64_t data_pos = hpos + hsize;
+        int64_t q = data_pos, bound_p = -1, bound_extent = 0, bound_walked = 0;
+        int bound_eager = 0, ended = 0;
+        uint64_t u = 0;
+        while (q < n && bound_p < 0 && !(E >= data_pos && E < q)) {
+            const uint32_t ctl = in[q];
+            int64_t hdr = 1, body = 0, front = 1; /* front: bytes taken in the call that ended the chunk before (header, the coder's first five) */
+            uint64_t us = 0;
+            if (ctl >= 0x80) {
+                hdr = ctl >= 0xC0 ? 6 : 5;
+                if (q + hdr > n)
+                    break;
+                us = ((uint64_t)(ctl & 0x1Fu) << 16) + ((uint64_t)in[q + 1] << 8) + in[q + 2] + 1u;
+                body = ((int64_t)in[q + 3] << 8) + in[q + 4] + 1;
+                front = hdr + (body < 5 ? body : 5);
+            } else if (ctl != 0) {
+                if (ctl > 2 || q + 3 > n)
+                    break;
+                hdr = front = 3;
+                us = ((uint64_t)in[q + 1] << 8) + in[q + 2] + 1u;
+                body = (int64_t)us;
+            }
+            const int64_t chunk_end = q + hdr + body; /* (from the chunk's size field: may lie behind the input) */
+            /* the bound is run into with the first byte behind the declared size: where the input ends in front of that byte
+             * liblzma never takes it, and the refusal stays where the device says (nothing below reads in[] from c on) */
+            if (want_c != ~0ull && (uint64_t)(chunk_end - data_pos) > want_c && want_c < (uint64_t)(n - data_pos)) {
+                const int64_t c = data_pos + (int64_t)want_c; /* the first byte behind the declared size */
+                bound_extent = c + 1;
+                bound_walked = q;
+                if (c < q + front) {
+                    bound_p = opos + (int64_t)u;
+                    bound_eager = q > data_pos; /* (liblzma does not start on a block's first chunk without room in the output) */
+                } else if (ctl < 0x80) {
+                    bound_p = opos + (int64_t)u + (c - (q + 3));
+                } else if (in[hpos + 1] & 3) { /* filters in front of LZMA2: what their chain hands out of the entry cut there */
+                    uint8_t *tmp = (uint8_t *)malloc((size_t)(z->out_cap > 0 ? z->out_cap : 1));
+                    uint32_t ol = 0, iu = 0, crc = 0;
+                    if (!tmp)
+                        return;
+                    (void)mzhip_xz_host(in, (uint32_t)c, tmp, (uint32_t)z->out_cap, -1, &ol, &iu, &crc);
+                    free(tmp);
+                    bound_p = (int64_t)ol;
+                } else { /* the block's chunks with no byte behind the declared size: how far they decode, and where they ask for it */
+                    const int64_t cap = (int64_t)(u + us) + 1024;
+                    uint8_t *tmp = (uint8_t *)malloc((size_t)cap);
+                    void *model = malloc(mzhip_lzma_model_bytes());
+                    mzhip_lzma2_state sin, sout;
+                    mzhip_lzma2_run_args a;
+                    uint32_t ol = 0, iu = 0;
+                    memset(&sin, 0, sizeof(sin));
+                    memset(&sout, 0, sizeof(sout));
+                    memset(&a, 0, sizeof(a));
+                    sin.flags = 4u | 8u | 2u;
+                    sin.dict = dict32;
+                    a.size = (uint32_t)sizeof(a);
+                    a.in = in + data_pos;
+                    a.in_len = (uint32_t)want_c;
+                    a.buf = tmp;
+                    a.buf_cap = (uint32_t)cap;
+                    a.state_in = &sin;
+                    a.state_out = &sout;
+                    a.model = model;
+                    a.out_len = &ol;
+                    a.in_used = &iu;
+                    if (!tmp || !model || cap > 0x7FFFFFFF) {
+                        free(tmp);
+                        free(model);
+                        return;
+                    }
+                    (void)mzhip_lzma2_run_host(&a);
+                    free(tmp);
+                    free(model);
+                    bound_p = opos + (int64_t)ol;
+                    bound_eager = (sout.flags & 256u) != 0; /* in the normalisation in front of a packet: liblzma normalises when the caller's buffer is full */
+                }
+            }
+            if (want_u != ~0ull && u + us > want_u && (bound_p < 0 || opos + (int64_t)want_u < bound_p)) {
+                bound_p = opos + (int64_t)want_u;
+                bound_eager = 0;
+            }
+            q = chunk_end;
+            u += us;
+            if (ctl == 0) {
+                ended = 1;
+                break;
+            }
+        }
+        if (bound_p >= 0 && (bound_p < D || (bound_p == D && bound_eager))) {
+            fail_p = bound_p;
+            z->xz_fail_bound = 1;
+            eager = bound_eager;
+            extent = bound_extent;
+            walked = bound_walked;
+            break;
+        }
+        if (!ended || q > n || E < q)
+            return; /* inside the block's chunks: where the device says, in the call that would go past it */
+        const int64_t next = q + ((data_pos - q) & 3) + check_size;
+        if (E < next) { /* sizes, block padding, check: behind the block's last bytes */
+            eager = 1;
+            walked = q;
+            extent = E == q ? q : E < next - check_size ? E + 1 : next;
+            break;
+        }
+        walked = q;
+        opos += (int64_t)u;
+        pos = next;
+    }
+    /* what the read() path relies on: the refusal lies inside the bytes the device made (it serves out[0 .. xz_fail_p)), and the
+     * walk ends inside the input.  A walk that says otherwise has misread the entry: as the device says */
+    if (fail_p < 0 || fail_p > D) {
+        z->xz_fail_bound = 0;
+        return;
+    }
+    if (extent > n)
+        extent = n; /* (a check field or an index the input breaks off in: the walk read what there is) */
+    if (eager && fail_p > 0) { /* ... as far as the input staged with those bytes reaches */
+        int64_t lim = walked > 0 ? ((walked - 1) / MZH_STAGING_BYTES + 1) * MZH_STAGING_BYTES : MZH_STAGING_BYTES;
+        if (z->max_total_in > 0 && lim > z->max_total_in)
+            lim = z->max_total_in;
+        if (extent > lim)
+            eager = 0;
+    }
+    z->xz_fail_p = fail_p;
+    z->xz_fail_eager = (int8_t)eager;
+}
+
 int32_t mz_stream_lzma_read(void *stream, void *buf, int32_t size) {
     mzhip_lzma *z = (mzhip_lzma *)stream;
     mzhip_served_drop();
@@ -947,6 +1227,20 @@ int32_t mz_stream_lzma_read(void *stream, void *buf, int32_t size) {
             z->next_attempt = z->in_len * 2;
     }
     int64_t avail = z->out_len - z->out_served;
+    if (z->method == MZH_COMPRESS_METHOD_XZ && z->dev_status == MZHIP_STATUS_DATA_ERROR && !z->out_borrowed) {
+        if (!z->xz_located)
+            xz_locate_refusal(z);
+        const int64_t reach = z->out_served + size; /* this call would make bytes [out_served, reach) */
+        if (z->xz_fail_eager ? reach >= z->xz_fail_p : reach > z->xz_fail_p) {
+            z->error = 9; /* LZMA_DATA_ERROR (what liblzma calls this refusal -- LZMA_OPTIONS_ERROR for some -- is not mirrored) */
+            z->total_in = z->dev_in_used;
+            z->total_out = (z->xz_fail_eager && !z->xz_fail_bound) ? z->xz_fail_p : (reach < z->out_len ? reach : z->out_len);
+            if (z->max_total_out >= 0 && z->total_out > z->max_total_out)
+                z->total_out = z->max_total_out;
+            return MZH_DATA_ERROR;
+        }
+        avail = z->xz_fail_p - z->out_served; /* (>= size: served below) */
+    }
     /* (method 14: liblzma is not told the entry's size, so with the caller's buffer full it still decodes the next packet to
      * see whether it is the end marker (lzma_decoder.c, SEQ_IS_MATCH without no_eopm) -- and a packet it refuses is refused
      * THERE: the call that returns the last bytes in front of a data error fails even when they fill the buffer.  LZMA2

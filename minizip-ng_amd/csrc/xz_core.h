@@ -240,12 +240,12 @@ MZ_DEV uint32_t mz_xz_unfilter(mz_xz_filter *f, uint8_t *b, uint32_t n, uint32_t
  * about being correct, so it is a call, not inline code -- inlined into mz_xz_entry it cost the hot decode loop 24 VGPRs
  * (161 -> 185) and 36 more parked SGPRs. */
 #if defined(MZHIP_HOST_EMUL)
-static void
+static uint32_t
 #else
-__device__ __noinline__ void
+__device__ __noinline__ uint32_t
 #endif
 mz_xz_unfilter_block(uint8_t *blk, uint32_t usize_blk, uint32_t npre, uint32_t fids, uint32_t farg0, uint32_t farg1, uint32_t farg2,
-                     uint8_t *fb) {
+                     uint8_t *fb, uint32_t partial) {
     MZ_LANE_DECL
     uint8_t *hist = fb + MZ_XZ_FCHUNK + 16u; /* MZ_XZ_FCHUNK + 16 bytes of staging, Delta's 256-byte ring behind it */
     for (uint32_t fi = 3u; fi-- > 0u;) {
@@ -287,8 +287,12 @@ mz_xz_unfilter_block(uint8_t *blk, uint32_t usize_blk, uint32_t npre, uint32_t f
             done += fin;
             if (fin == 0u && take == 0u) break;
         }
-        /* what is left in the carry never had enough bytes behind it: it stays as it is */
+        /* what is left in the carry never had enough bytes behind it: it stays as it is -- final when the block is complete;
+         * of a block that broke off (partial) liblzma's filter still holds those bytes back, and the filter in front of it
+         * has not seen them */
+        if (partial) usize_blk = done;
     }
+    return usize_blk;
 }
 
 
@@ -322,6 +326,7 @@ MZ_DEV void mz_xz_entry(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32
     PV(uint32_t, crc_tmp);
     uint32_t crc_done = 0;
     uint32_t crc_hold = 0xFFFFFFFFu; /* the fused CRC folds no further than this (start of a filtered block in progress) */
+    uint32_t fids = 0, farg0 = 0, farg1 = 0, farg2 = 0, npre = 0; /* the block's filters in front of LZMA2: id of filter k in bits 8k .. 8k + 7 */
     MZ_LANES {
         P(crc_acc) = (lane == 0) ? 0xFFFFFFFFu : 0u;
         P(win) = 0;
@@ -369,7 +374,7 @@ MZ_DEV void mz_xz_entry(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32
             /* what the header says of them is an id and one argument each; the filters' running state starts from
              * constants when the block is unfiltered (mz_xz_unfilter_block) -- four wave-uniform words live across the block's
              * decode loop instead of the fifteen of three filter structs */
-            uint32_t fids = 0, farg0 = 0, farg1 = 0, farg2 = 0, npre = 0; /* id of filter k in bits 8k .. 8k + 7 */
+            fids = farg0 = farg1 = farg2 = npre = 0;
             mz_xz_filter fnew;
 #define XZ_PUSH_FILTER()                         \
     do {                                         \
@@ -539,7 +544,7 @@ MZ_DEV void mz_xz_entry(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32
             if ((want_csize != ~0ull && want_csize != csize_blk) || (want_usize != ~0ull && want_usize != usize_blk))
                 goto finish;
             if (npre) {
-                mz_xz_unfilter_block(out + block_out, usize_blk, npre, fids, farg0, farg1, farg2, (uint8_t *)pr);
+                mz_xz_unfilter_block(out + block_out, usize_blk, npre, fids, farg0, farg1, farg2, (uint8_t *)pr, 0u);
                 crc_hold = 0xFFFFFFFFu;
             }
             while ((pos - data_pos) & 3u) {
@@ -616,9 +621,11 @@ finish:
     {
         uint32_t olen = opos;
         /* an exit inside a block whose filters are not undone yet (output full, a data error, short input): the bytes
-         * from the start of that block on are still in the filtered domain -- liblzma streams its filter chain and would
-         * never have shown them -- so the result ends where the block began (crc_hold) */
-        if (crc_hold != 0xFFFFFFFFu && olen > crc_hold) olen = crc_hold;
+         * from the start of that block on are still in the filtered domain.  liblzma streams its filter chain: it has
+         * handed out what the chain could finish of them and holds the rest back (a BCJ filter its last few bytes), so
+         * the chain is run over what there is and the result ends where it got to */
+        if (crc_hold != 0xFFFFFFFFu && olen > crc_hold)
+            olen = crc_hold + mz_xz_unfilter_block(out + crc_hold, olen - crc_hold, npre, fids, farg0, farg1, farg2, (uint8_t *)pr, 1u);
         if (max_out >= 0 && (int64_t)olen > max_out) olen = (uint32_t)max_out; /* mz_strm_lzma.c:214-215 */
         if (status == MZHIP_DATA_ERROR && eof && rc_short) {
             /* the coder ran off a chunk that the input does not hold completely: input ended early */
@@ -656,7 +663,9 @@ typedef struct mz_lzma2_state {
                          32 inside an uncompressed chunk, 64 inside an LZMA chunk; out: the same, 1 = a state to go on
                          from, 16 = the block's end byte has been consumed, 128 = the data error was met between chunks
                          (control byte, chunk header, the coder's first bytes, its state at the chunk's end) and not
-                         inside a packet: liblzma meets those without room in the output */
+                         inside a packet: liblzma meets those without room in the output; set likewise when the input ran out there
+                         (MZHIP_BUF_ERROR), 256 = the input ran out in the normalisation in front of a packet: liblzma
+                         normalises when the caller's buffer is full, so it too asks for that byte without room in the output */
     uint32_t range, code, state;
     uint32_t rep0, rep1, rep2, rep3;
     uint32_t props;   /* lc | lp << 8 | pb << 16 */
@@ -678,6 +687,8 @@ typedef struct mz_lzma2_state {
     }
 #undef LZ_CRC_LIMIT
 #define LZ_CRC_LIMIT(o) 0u /* no fused CRC: the block's check is folded when the window is done */
+#undef LZ_FIRST_BIT_DONE
+#define LZ_FIRST_BIT_DONE() do { if (eof) eof_norm = 1u; } while (0)
 MZ_DEV void mz_lzma2_run(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, mz_xz_lds *L,
                          const uint32_t *crc_tab, const mzhip_crc_tables *tabs, uint16_t *model, const mz_lzma2_state *rs,
                          mz_lzma2_state *st, mz_lzma_result *res) {
@@ -691,6 +702,8 @@ MZ_DEV void mz_lzma2_run(const uint8_t *in, uint32_t in_len, uint8_t *out, uint3
     uint32_t need_props = (fin >> 2) & 1u, need_dict_reset = (fin >> 3) & 1u;
     uint32_t in_raw = (fin >> 5) & 1u, in_lz = (fin >> 6) & 1u;
     uint32_t stopped = 0, ended = 0;
+    uint32_t eof_norm = 0; /* the input ran out in the normalisation in front of a packet */
+    uint32_t coder_start = 0; /* a chunk's header has been read, its coder is taking its first five bytes */
     uint32_t front = 1; /* between packets of different chunks: control byte, chunk header, coder start and end */
     uint32_t pos = 0; /* cursor in `in` */
     uint32_t opos = MZ_UNIFORM(rs->out_pos);
@@ -729,6 +742,7 @@ MZ_DEV void mz_lzma2_run(const uint8_t *in, uint32_t in_len, uint8_t *out, uint3
     for (;;) {
         if (in_raw) {
             /* ---- the rest of an uncompressed chunk ---- */
+            front = 0;
             uint32_t n = usize_left, stop = 0;
             if (n > in_len - pos) {
                 n = in_len - pos;
@@ -751,6 +765,7 @@ MZ_DEV void mz_lzma2_run(const uint8_t *in, uint32_t in_len, uint8_t *out, uint3
                 goto finish;
             }
             in_raw = 0;
+            front = 1;
             continue;
         }
         if (!in_lz) {
@@ -841,6 +856,7 @@ MZ_DEV void mz_lzma2_run(const uint8_t *in, uint32_t in_len, uint8_t *out, uint3
                 rep0 = rep1 = rep2 = rep3 = 0;
             }
             /* the chunk's compressed bytes are one self-contained range-coder run */
+            coder_start = 1;
             rc_short = (in_len - pos) < csize;
             rc_partial = rc_short && !last_input;
             rc_in = in + pos;
@@ -875,6 +891,7 @@ MZ_DEV void mz_lzma2_run(const uint8_t *in, uint32_t in_len, uint8_t *out, uint3
         match_byte = (state >= 7 && rep0 < opos - dict_start) ? MZ_UNIFORM(out[opos - rep0 - 1]) : 0u;
         if (eof) goto finish;
         front = 0;
+        coder_start = 0;
         LZ_PACKET_LOOP();
         front = 1;
         LZ_NORM(); /* liblzma normalises once more before it requires the coder to hold 0 */
@@ -899,6 +916,10 @@ finish:
         pos = in_len;
     } else if (!stopped && !ended && in_pos != 0u) {
         pos += in_pos > rc_len ? rc_len : in_pos; /* a failed chunk: as far as the coder had read */
+    }
+    if (!stopped && !ended && (!front || coder_start)) { /* broke off inside an LZMA chunk: what it still owed (not a state to go on from) */
+        if (!front) usize_left = chunk_end > opos ? chunk_end - opos : 0u;
+        csize_left = csize - (in_pos > rc_len ? rc_len : in_pos);
     }
     {
         /* the block's check over this window's bytes, taken up from the windows before */
@@ -925,7 +946,8 @@ finish:
         }
         MZ_LANES { /* uniform stores */
             st->flags = stopped | (need_props << 2) | (need_dict_reset << 3) | (ended << 4) | (in_raw << 5) | (in_lz << 6) |
-                        ((status == MZHIP_DATA_ERROR && front) ? 128u : 0u);
+                        (((status == MZHIP_DATA_ERROR || status == MZHIP_BUF_ERROR) && front) ? 128u : 0u) |
+                        ((status == MZHIP_BUF_ERROR && eof_norm && !front && !stopped) ? 256u : 0u);
             st->range = range;
             st->code = code;
             st->state = state;
@@ -954,6 +976,8 @@ finish:
 }
 #undef LZ_RESUME_CHECK
 #define LZ_RESUME_CHECK() ((void)0)
+#undef LZ_FIRST_BIT_DONE
+#define LZ_FIRST_BIT_DONE() ((void)0)
 #undef LZ_CRC_LIMIT
 #define LZ_CRC_LIMIT(o) (o)
 

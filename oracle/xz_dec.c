@@ -226,14 +226,15 @@ static int32_t lzma2_block(lz_t *z, cur_t *c) {
 
 /* ---- the filters in front of LZMA2, decoding direction, over one whole block (a filter only looks at the bytes and at
  * their position in the block, so one call over the block equals liblzma's buffered calls) ---- */
-static void unfilter_delta(uint8_t *b, size_t n, unsigned dist) {
+static size_t unfilter_delta(uint8_t *b, size_t n, unsigned dist) {
     for (size_t i = dist; i < n; i++) b[i] = (uint8_t)(b[i] + b[i - dist]);
+    return n;
 }
 static int msbyte86(uint8_t b) { return b == 0 || b == 0xFF; }
-static void unfilter_x86(uint8_t *b, size_t n, uint32_t now) {
+static size_t unfilter_x86(uint8_t *b, size_t n, uint32_t now) {
     static const uint8_t allowed[8] = {1, 1, 1, 0, 1, 0, 0, 0}, bitnum[8] = {0, 1, 2, 2, 3, 3, 3, 3};
     uint32_t prev_mask = 0, prev_pos = (uint32_t)-5;
-    if (n < 5) return;
+    if (n < 5) return 0;
     if (now - prev_pos > 5) prev_pos = now - 5;
     const size_t limit = n - 5;
     size_t i = 0;
@@ -276,9 +277,11 @@ static void unfilter_x86(uint8_t *b, size_t n, uint32_t now) {
             if (msbyte86(c)) prev_mask |= 0x10;
         }
     }
+    return i;
 }
-static void unfilter_powerpc(uint8_t *b, size_t n, uint32_t now) {
-    for (size_t i = 0; i + 4 <= n; i += 4)
+static size_t unfilter_powerpc(uint8_t *b, size_t n, uint32_t now) {
+    size_t i;
+    for (i = 0; i + 4 <= n; i += 4)
         if ((b[i] >> 2) == 0x12 && (b[i + 3] & 3) == 1) {
             const uint32_t src = ((uint32_t)(b[i] & 3) << 24) | ((uint32_t)b[i + 1] << 16) | ((uint32_t)b[i + 2] << 8) | (b[i + 3] & ~3u);
             const uint32_t dest = src - (now + (uint32_t)i);
@@ -287,10 +290,12 @@ static void unfilter_powerpc(uint8_t *b, size_t n, uint32_t now) {
             b[i + 2] = (uint8_t)(dest >> 8);
             b[i + 3] = (uint8_t)((b[i + 3] & 3) | (dest & ~3u));
         }
+    return i;
 }
-static void unfilter_ia64(uint8_t *b, size_t n, uint32_t now) {
+static size_t unfilter_ia64(uint8_t *b, size_t n, uint32_t now) {
     static const uint8_t branch[32] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 4, 4, 6, 6, 0, 0, 7, 7, 4, 4, 0, 0, 4, 4, 0, 0};
-    for (size_t i = 0; i + 16 <= n; i += 16) {
+    size_t i;
+    for (i = 0; i + 16 <= n; i += 16) {
         const uint32_t mask = branch[b[i] & 0x1F];
         uint32_t bit_pos = 5;
         for (unsigned slot = 0; slot < 3; slot++, bit_pos += 41) {
@@ -315,9 +320,11 @@ static void unfilter_ia64(uint8_t *b, size_t n, uint32_t now) {
             }
         }
     }
+    return i;
 }
-static void unfilter_arm(uint8_t *b, size_t n, uint32_t now) {
-    for (size_t i = 0; i + 4 <= n; i += 4)
+static size_t unfilter_arm(uint8_t *b, size_t n, uint32_t now) {
+    size_t i;
+    for (i = 0; i + 4 <= n; i += 4)
         if (b[i + 3] == 0xEB) {
             uint32_t src = ((uint32_t)b[i + 2] << 16) | ((uint32_t)b[i + 1] << 8) | b[i];
             src <<= 2;
@@ -327,9 +334,11 @@ static void unfilter_arm(uint8_t *b, size_t n, uint32_t now) {
             b[i + 1] = (uint8_t)(dest >> 8);
             b[i] = (uint8_t)dest;
         }
+    return i;
 }
-static void unfilter_armthumb(uint8_t *b, size_t n, uint32_t now) {
-    for (size_t i = 0; i + 4 <= n; i += 2)
+static size_t unfilter_armthumb(uint8_t *b, size_t n, uint32_t now) {
+    size_t i;
+    for (i = 0; i + 4 <= n; i += 2)
         if ((b[i + 1] & 0xF8) == 0xF0 && (b[i + 3] & 0xF8) == 0xF8) {
             uint32_t src = ((uint32_t)(b[i + 1] & 7) << 19) | ((uint32_t)b[i] << 11) | ((uint32_t)(b[i + 3] & 7) << 8) | b[i + 2];
             src <<= 1;
@@ -341,9 +350,11 @@ static void unfilter_armthumb(uint8_t *b, size_t n, uint32_t now) {
             b[i + 2] = (uint8_t)dest;
             i += 2;
         }
+    return i;
 }
-static void unfilter_sparc(uint8_t *b, size_t n, uint32_t now) {
-    for (size_t i = 0; i + 4 <= n; i += 4)
+static size_t unfilter_sparc(uint8_t *b, size_t n, uint32_t now) {
+    size_t i;
+    for (i = 0; i + 4 <= n; i += 4)
         if ((b[i] == 0x40 && (b[i + 1] & 0xC0) == 0x00) || (b[i] == 0x7F && (b[i + 1] & 0xC0) == 0xC0)) {
             uint32_t src = ((uint32_t)b[i] << 24) | ((uint32_t)b[i + 1] << 16) | ((uint32_t)b[i + 2] << 8) | b[i + 3];
             src <<= 2;
@@ -355,6 +366,27 @@ static void unfilter_sparc(uint8_t *b, size_t n, uint32_t now) {
             b[i + 2] = (uint8_t)(dest >> 8);
             b[i + 3] = (uint8_t)dest;
         }
+    return i;
+}
+/* the chain over the n bytes of a block there are, last applied first.  whole: the block is complete, every byte is final (what
+ * a filter could not finish stays as it is).  Otherwise the block broke off: liblzma's filters still hold back what they
+ * could not finish, and the filter in front has not seen those bytes.  -> the bytes that are final */
+static size_t unfilter_chain(uint8_t *b, size_t n, const unsigned *id, const uint32_t *arg, unsigned npre, int whole) {
+    for (unsigned f = npre; f-- > 0;) {
+        size_t got;
+        switch (id[f]) {
+        case 3: got = unfilter_delta(b, n, arg[f]); break;
+        case 4: got = unfilter_x86(b, n, arg[f]); break;
+        case 5: got = unfilter_powerpc(b, n, arg[f]); break;
+        case 6: got = unfilter_ia64(b, n, arg[f]); break;
+        case 7: got = unfilter_arm(b, n, arg[f]); break;
+        case 8: got = unfilter_armthumb(b, n, arg[f]); break;
+        default: got = unfilter_sparc(b, n, arg[f]); break;
+        }
+        if (!whole)
+            n = got;
+    }
+    return n;
 }
 
 int32_t orc_xz_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, int64_t max_out, size_t *in_used,
@@ -362,6 +394,9 @@ int32_t orc_xz_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out
     static const uint8_t magic[6] = {0xFD, '7', 'z', 'X', 'Z', 0x00};
     int32_t ret = ORC_DATA_ERROR;
     cur_t c = {in, in_len, 0, 0};
+    size_t cut_pos0 = 0; /* a filtered block in progress: where it began in out, and its chain */
+    unsigned cut_npre = 0, cut_id[3] = {0, 0, 0};
+    uint32_t cut_arg[3] = {0, 0, 0};
     lz_t *z = (lz_t *)calloc(1, sizeof(lz_t));
     if (!z)
         return ORC_DATA_ERROR;
@@ -414,8 +449,8 @@ int32_t orc_xz_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out
             p += used;
         }
         uint64_t dict = 0;
-        unsigned pre_id[3], npre = 0; /* the filters in front of LZMA2, in header order */
-        uint32_t pre_arg[3];          /* delta: distance; BCJ: start offset */
+        unsigned pre_id[3] = {0, 0, 0}, npre = 0; /* the filters in front of LZMA2, in header order */
+        uint32_t pre_arg[3] = {0, 0, 0};          /* delta: distance; BCJ: start offset */
         const unsigned nfilt = (bflags & 3u) + 1u;
         for (unsigned f = 0; f < nfilt; f++) {
             uint64_t id, psize;
@@ -461,6 +496,10 @@ int32_t orc_xz_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out
 
         /* compressed data, padding to a multiple of four, check */
         const size_t data_pos = c.pos, out_pos0 = z->opos;
+        cut_pos0 = out_pos0; /* (an exit from here on leaves a block whose filters are not undone) */
+        cut_npre = npre;
+        memcpy(cut_id, pre_id, sizeof(cut_id));
+        memcpy(cut_arg, pre_arg, sizeof(cut_arg));
         int32_t r = lzma2_block(z, &c);
         if (r != ORC_OK) {
             ret = r;
@@ -469,19 +508,8 @@ int32_t orc_xz_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out
         const uint64_t csize = c.pos - data_pos, usize = z->opos - out_pos0;
         if ((want_csize != UINT64_MAX && want_csize != csize) || (want_usize != UINT64_MAX && want_usize != usize))
             goto done;
-        for (unsigned f = npre; f-- > 0;) { /* undo the filters, last applied first */
-            uint8_t *b = out + out_pos0;
-            const size_t n = (size_t)usize;
-            switch (pre_id[f]) {
-            case 3: unfilter_delta(b, n, pre_arg[f]); break;
-            case 4: unfilter_x86(b, n, pre_arg[f]); break;
-            case 5: unfilter_powerpc(b, n, pre_arg[f]); break;
-            case 6: unfilter_ia64(b, n, pre_arg[f]); break;
-            case 7: unfilter_arm(b, n, pre_arg[f]); break;
-            case 8: unfilter_armthumb(b, n, pre_arg[f]); break;
-            default: unfilter_sparc(b, n, pre_arg[f]); break;
-            }
-        }
+        unfilter_chain(out + out_pos0, (size_t)usize, pre_id, pre_arg, npre, 1); /* undo the filters */
+        cut_npre = 0;
         while ((c.pos - data_pos) & 3) {
             if (!need(&c, 1)) {
                 ret = ORC_BUF_ERROR;
@@ -574,6 +602,10 @@ int32_t orc_xz_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out
     }
 
 done:
+    /* an exit inside a block whose filters are not undone (short input, a data error, output full): liblzma streams its
+     * chain and has handed out what the chain could finish of the block's bytes */
+    if (cut_npre && z->opos > cut_pos0)
+        z->opos = cut_pos0 + unfilter_chain(out + cut_pos0, z->opos - cut_pos0, cut_id, cut_arg, cut_npre, 0);
     if (in_used)
         *in_used = c.pos;
     if (out_len)

@@ -8,6 +8,7 @@
 // stand-in for the HIP runtime).  What it cannot cover: the write-side prime (mzhip_prime.cpp) and the .xz writer, whose
 // host code launches kernels itself (mzhip_launch.inc).
 #include <atomic>
+#include <vector>
 
 #include "emul.cpp"
 
@@ -309,6 +310,13 @@ MOCK_API int32_t mzhip_lzma2_run_host(const mzhip_lzma2_run_args *ap) {
     if (!a.model || !a.state_in || !a.state_out || !a.buf || a.state_in->out_pos > a.buf_cap) return -102;
     uint32_t ol = 0, iu = 0;
     g_mock_lzma2_windows++;
+    /* the runtime copies all in_len bytes to the device before it decodes: so does the stand-in, and a caller that names more
+     * bytes than it holds reads behind its buffer here as it would there */
+    std::vector<uint8_t> staged;
+    if (a.in && a.in_len) {
+        staged.assign(a.in, a.in + a.in_len);
+        a.in = staged.data();
+    }
     const uint8_t dummy = 0;
     const int32_t st = emul_lzma2_run(a.in ? a.in : &dummy, a.in_len, a.buf, a.buf_cap, (const uint32_t *)a.state_in, (uint32_t *)a.state_out,
                                       (uint16_t *)a.model, &ol, &iu);
@@ -332,6 +340,11 @@ MOCK_API int32_t mzhip_lzma_encode_resume_host(const uint8_t *in, uint32_t in_le
 MOCK_API int32_t mzhip_xz_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, int64_t max_out,
                                uint32_t *out_len, uint32_t *in_used, uint32_t *crc) {
     uint32_t ol = 0, iu = 0, k = 0;
+    std::vector<uint8_t> staged; /* (all in_len bytes are read, as the runtime's copy reads them) */
+    if (in && in_len) {
+        staged.assign(in, in + in_len);
+        in = staged.data();
+    }
     const int32_t st = emul_xz(in, in_len, out, out_cap, max_out, &ol, &iu, &k);
     if (out_len) *out_len = ol;
     if (in_used) *in_used = iu;
