@@ -29,6 +29,7 @@
     /* far: sources older than the chunk; what remains of a piece goes back to the list, compacted */
     uint32_t nnear = 0;
     for (uint32_t b = 0; b < Tm && !fail; b += 64u) {
+        MZ_STAT(26, 1); /* far batches */
         PV(uint32_t, e0);
         PV(uint32_t, rem);
         MZ_LANES {
@@ -81,6 +82,7 @@
      * +0.7 % on the device: profiles/r5/call14_probe.log) */
 #if !(MZ_ABLATE & 1)
     for (uint32_t b = 0; b < nnear && !fail; b += 64u) {
+        MZ_STAT(25, 1); /* near batches */
         PV(uint32_t, d0);
         PV(uint32_t, rem);
         PV(uint32_t, dist);
@@ -106,6 +108,40 @@
             P(ca) = 0u;
             P(cb) = 0u;
         }
+#if MZ_NEAR_PACKED
+        /* The same two searches with ca and cb kept as BYTE offsets of the cross-lane gather (4 * rank: what ds_bpermute
+         * takes), so a step is add, gather, compare, add per query and nothing is shifted or masked on the way; the first
+         * step asks every lane for lane 31, which is a scalar read.  (One gather per step cannot serve both queries, packed
+         * keys or not: after the first step ca and cb of a lane stand at different ranks, and a gather hands a lane the
+         * register of ONE other lane.) */
+        {
+            PV(uint32_t, s0);
+            PV(uint32_t, s1);
+            const uint32_t ke31 = MZ_READLANE(ken, 31), ks31 = MZ_READLANE(kst, 31);
+            MZ_LANES {
+                /* the part of the source that is not this piece's own output */
+                P(s0) = P(d0) - P(dist);
+                P(s1) = P(s0) + ((P(rem) < P(dist)) ? P(rem) : P(dist));
+                P(ca) = (ke31 <= P(s0)) ? 128u : 0u;
+                P(cb) = (ks31 < P(s1)) ? 128u : 0u;
+            }
+#pragma unroll
+            for (uint32_t step = 64u; step != 2u; step >>= 1) { /* 4 * (16, 8, 4, 2, 1) */
+                PV(uint32_t, va);
+                PV(uint32_t, vb);
+                MZ_GATHER4(va, ken, P(ca) + (step - 4u));
+                MZ_GATHER4(vb, kst, P(cb) + (step - 4u));
+                MZ_LANES {
+                    if (P(va) <= P(s0)) P(ca) += step;
+                    if (P(vb) < P(s1)) P(cb) += step;
+                }
+            }
+            MZ_LANES {
+                P(ca) >>= 2;
+                P(cb) >>= 2;
+            }
+        }
+#else
 #pragma unroll
         for (uint32_t step = 32u; step != 0u; step >>= 1) {
             PV(uint32_t, va);
@@ -119,6 +155,7 @@
                 if (P(vb) < s1) P(cb) += step;
             }
         }
+#endif
         MZ_LANES {
             /* (cb <= lane: a piece's source ends where its output starts at the latest) */
             P(dep) = (P(cb) > P(ca)) ? ((~0ull >> (64u - (P(cb) - P(ca)))) << P(ca)) : 0ull;
@@ -142,7 +179,13 @@
                     if (D < 8u) {
                         /* short period: byte by byte until a multiple of the period reaches 8, then the
                          * same 8-byte steps at that distance (every byte equals the one D' behind it) */
+#if MZ_NEAR_PACKED
+                        /* D8 - D for D = 1 .. 7 is 7, 6, 6, 4, 5, 6, 7 (D8 = 8, 8, 9, 8, 10, 12, 14): a nibble each of
+                         * one constant, where the line below divides by a variable (a reciprocal sequence on the device) */
+                        const uint32_t D8 = D + ((0x76546670u >> (4u * D)) & 15u);
+#else
                         const uint32_t D8 = D * ((7u + D) / D);
+#endif
                         uint32_t pro = D8 - D;
                         if (pro > n) pro = n;
                         for (uint32_t k = 0; k < pro; k++) d[k] = d[(int32_t)k - (int32_t)D];

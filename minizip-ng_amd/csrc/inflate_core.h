@@ -146,6 +146,15 @@ extern __device__ unsigned long long mz_prof_buf[32];
 #undef MZ_WALK_TRIP_REFILL
 #define MZ_WALK_TRIP_REFILL 0
 #endif
+#ifndef MZ_CHASE_LEAN
+#define MZ_CHASE_LEAN 1 /* pass 2 of the walks (inflate_walk.inc): 1 = a chase whose target lane's walk is over takes the next target at the
+                           top of the next trip, once per trip; 0 = inside each of the trip's four steps (round 4 .. 9) */
+#endif
+#ifndef MZ_NEAR_PACKED
+#define MZ_NEAR_PACKED 1 /* the near batches of the commit (inflate_commit.inc): 1 = the rank searches keep byte offsets for the gather
+                            and start with a scalar read, the short-period prologue takes its length from a packed constant;
+                            0 = shifted lane indices and a division by the distance (round 5 .. 9) */
+#endif
 #ifndef MZ_EMIT_GROUP
 #define MZ_EMIT_GROUP 8u /* records one lane turns into bytes per emit round (4 or 8: records are stored in quads) */
 #endif

@@ -403,6 +403,18 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         P(dst)[2] = v_.v[2];                                                                 \
         P(dst)[3] = v_.v[3];                                                                 \
     }
+#if MZ_CHASE_LEAN
+    /* (MZ_CHASE_LEAN 1: a target is taken in front of a trip only, where the window of lengths moves on anyway -- its first
+     * sixteen lengths are asked for as the load in flight, and the renewal right behind hands them over) */
+#define MZ_CHASE_TARGET(lane_)                                                               \
+    {                                                                                        \
+        P(tt) = 0u;                                                                          \
+        P(uo) = Wu + (lane_) * S;                                                            \
+        P(tn) = tab_walk[(lane_)];                                                           \
+        P(pb) = 0u;                                                                          \
+        MZ_CHASE_LOAD_LEN(lp, (lane_), 0u)                                                   \
+    }
+#else
 #define MZ_CHASE_TARGET(lane_)                                                               \
     {                                                                                        \
         P(tt) = 0u;                                                                          \
@@ -416,6 +428,7 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         P(lp)[2] = P(lw)[2];                                                                 \
         P(lp)[3] = P(lw)[3];                                                                 \
     }
+#endif
     MZ_LANES {
         P(chs) = ((uint32_t)lane + 1u < nact && P(sfl) == 0u) ? 1u : 0u;
         P(cm) = 0u;
@@ -441,6 +454,50 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         P(uo) += mz_bfe((ix_ & 8u) ? wb_ : wa_, 8u * (ix_ & 3u), 6); /* (the K byte's low six bits) */ \
         P(tt)++;                                                                             \
     }
+#if MZ_CHASE_LEAN
+    /* MZ_CHASE_LEAN 1: a step only ever STOPS a chase -- at a meeting point, an end of block, an invalid code -- and says how
+     * in cfl; it takes no new target (MZ_CHASE_RETARGET, in front of the trip) and copies nothing: a lane that has stopped
+     * replays no more, so tj and tt stay what they were at the meeting point and are read off behind the loop. */
+#define MZ_CHASE_STEP(K)                                                                     \
+    MZ_CHASE_REPLAY_ONE                                                                      \
+    MZ_CHASE_REPLAY_ONE                                                                      \
+    {                                                                                        \
+        const uint32_t on_ = P(tn) & 0xFFFFu, of_ = P(tn) >> 16;                             \
+        const uint32_t meet_ = (P(chs) != 0u && P(uo) == P(u) && (P(tt) < on_ || of_ == 0u)) ? 1u : 0u; \
+        P(cfl) = meet_ ? 0u : P(cfl);                                                        \
+        P(chs) = meet_ ? 0u : P(chs);                                                        \
+    }                                                                                        \
+    if (P(chs)) {                                                                            \
+        const uint32_t *const rp_ = P(row) + ((P(u) >> 5) & (MZ_CRING_DW - 1u));             \
+        uint32_t r_;                                                                         \
+        const uint32_t k_ = mz_chase_step(L, rp_[0], rp_[1], rp_[2], P(u), 64u, &r_);        \
+        const uint32_t ok_ = ((k_ & 63u) != 0u && P(u) + (k_ & 63u) <= Eu) ? 1u : 0u;        \
+        const uint32_t kk_ = ok_ ? k_ : 0u;                                                  \
+        P(rb)[(K)] = r_;                                                                     \
+        P(lacc) |= kk_ << (8 * (K));                                                         \
+        P(cm) += ok_;                                                                        \
+        P(u) += kk_ & 63u;                                                                   \
+        if (!ok_ || (k_ & MZ_K_EOB)) {                                                       \
+            P(cfl) = ok_ ? 1u : 2u;                                                          \
+            P(chs) = 0u;                                                                     \
+        }                                                                                    \
+    }
+    /* In front of a trip: a lane whose target's walk is over (it crossed behind the lane, or stopped for a reason of its
+     * own) and is no meeting point takes the next span's lane, or leaves the window.  See the proof at the loop. */
+#define MZ_CHASE_RETARGET                                                                    \
+    if (P(chs)) {                                                                            \
+        const uint32_t on_ = P(tn) & 0xFFFFu, of_ = P(tn) >> 16;                             \
+        if (P(tt) >= on_ && (P(uo) < P(u) || (P(uo) == P(u) && of_ != 0u))) {                \
+            P(tj)++;                                                                         \
+            MZ_STAT(27, 1); /* targets taken behind the first */                             \
+            if (P(tj) >= nact) {                                                             \
+                P(chs) = 0u; /* (cfl is still 4: only a lane that stops sets it) */          \
+            } else {                                                                         \
+                MZ_CHASE_TARGET(P(tj))                                                       \
+            }                                                                                \
+        }                                                                                    \
+    }
+#else
 #define MZ_CHASE_STEP(K)                                                                     \
     MZ_CHASE_REPLAY_ONE                                                                      \
     MZ_CHASE_REPLAY_ONE                                                                      \
@@ -455,6 +512,7 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         } else if (P(tt) >= on_ && P(uo) <= P(u)) {                                          \
             /* that lane's walk is over (it crossed behind us, or stopped for a reason of its own): on to the next span */ \
             P(tj)++;                                                                         \
+            MZ_STAT(27, 1);                                                                  \
             if (P(tj) >= nact) {                                                             \
                 P(cfl) = 4u;                                                                 \
                 P(chs) = 0u;                                                                 \
@@ -478,17 +536,72 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
             P(chs) = 0u;                                                                     \
         }                                                                                    \
     }
+#endif
     /* the trip before: its quad of records and its four K bytes (one dword into the lane's row of the chases' K stream) */
 #define MZ_CHASE_RETIRE_CHASE_TRIP(t_)                                                       \
     MZ_LANES {                                                                               \
         MZ_CHASE_STORE_QUAD(Cp, ((t_) - 4u) >> 2)                                            \
         if (P(lacc) != 0u) mz_st4(Lc + ((uint32_t)lane * MZ_REC_CAP2 + ((t_) - 4u)), P(lacc)); \
     }
+    /* MZ_CHASE_LEAN 1 -- ONE place per trip where a chase takes a new target, in front of the trip, where rounds 4 .. 9 had one
+     * in each of the four steps (a table read, a 16-byte load with its wait, and the copies that keep tj, tt, uo, csx, cst and
+     * cfl apart on every way through a step: ~18 register copies per step in every wave, retarget or not).
+     * WHAT CHANGES: only WHEN a lane starts to replay its next target -- up to three steps later.  WHAT DOES NOT: what the
+     * lane decodes.  A chasing lane decodes one step per step of the trip in either build, with or without a target to
+     * replay (the old step retargets and decodes on in the same step), so u after k steps, the records rb / lacc, their
+     * slots (step t2 + K of the chase is record t2 + K: no step is left out, so there are no holes in the quads or in the K
+     * stream), cm, and an end of block or invalid code with its cfl = 1 / 2 are the same step for step.  A lane that idled
+     * until the next trip instead would leave such holes; it must not.
+     * PROOF that the result of the window is a true parse all the same.  The chain (inflate_chase.inc) asks of a chase
+     * only this: cfl == 0 means that after cm recorded steps the cursor u stands where step cst of lane csx's own walk
+     * starts (or, cst == sn of a lane that crossed, where that walk ended); cfl != 0 means that after cm recorded steps the
+     * cursor is u, and why it stopped.  A step sets cfl = 0 under the very condition of rounds 4 .. 9 -- uo == u with uo the
+     * sum of the first tt lengths of lane tj's walk from its span's start, tt < on or the walk crossed -- and csx / cst are tj
+     * / tt of that moment, because a lane that stopped replays no more and takes no target (both ask for chs); they are
+     * read off behind the loop.  So every meeting point reported is one.  It may be a LATER one of the same two walks than
+     * before, or one with a later lane; the chain then follows this lane's records (the same tokens: two walks that stand
+     * on one token start decode the same from there) for longer before it changes over.  Leaving the window (tj reaches
+     * nact) is noticed up to three steps later: cm and u are those steps further on, valid steps each (ok_ asks for
+     * every one to end inside the input), and the next window starts there.  The record cap: a chase still running at
+     * t2 == MZ_REC_CAP2 gets cfl = 3 as before, now possibly one that would have met in its last steps; the chain ends
+     * there and the next window goes on from u with shorter spans -- slower, never different bytes.
+     *   A target that is over but IS a meeting point (uo == u, the walk crossed, tt == on) is left for step 0 to report: the
+     * retarget asks for uo < u, or uo == u behind a walk that stopped for a reason of its own.
+     * The window of lengths: lw holds sixteen lengths from step lb of the target on, lp the load in flight from pb on.  A
+     * trip advances tt by at most 8; lw was asked for one trip ago at tt of then, so tt - lb <= 15 throughout.  A new
+     * target asks for its first sixteen as the load in flight and the renewal right behind it hands them over (lb = 0,
+     * tt = 0) and asks again: no copy of the window outside the renewal. */
     uint32_t t2 = 0;
     for (;;) {
+#if MZ_CHASE_LEAN
+        MZ_LANES { MZ_CHASE_RETARGET }
+#endif
         uint64_t live;
         MZ_BALLOT(live, P(chs) != 0u);
         if (!live || t2 >= MZ_REC_CAP2) break;
+#if MZ_CHASE_LEAN
+        /* the same renewal in two halves with the compiler's memory barrier between them: the load is to go straight into
+         * lp's registers, which are free once lw has taken their values.  (In one piece the load was issued first, into
+         * registers of its own, and waited for on the spot to be copied into lp: the prefetch hid nothing.) */
+        MZ_LANES { /* (every lane, chasing or not: one wait for the load in flight that no path goes round) */
+            P(lw)[0] = P(lp)[0];
+            P(lw)[1] = P(lp)[1];
+            P(lw)[2] = P(lp)[2];
+            P(lw)[3] = P(lp)[3];
+            P(lb) = P(pb);
+            P(pb) = P(tt);
+#if !defined(MZHIP_HOST_EMUL)
+            /* (the copies stand HERE, with their wait, in front of the refill's loads: left to itself the compiler sinks them
+             * behind the refill and waits for the groups it has just asked for) */
+            asm volatile("" : "+v"(lw[0]), "+v"(lw[1]), "+v"(lw[2]), "+v"(lw[3]) : : "memory");
+#endif
+        }
+        MZ_LANES { MZ_CHASE_REFILL(P(chs)) } /* (in front of the load: its wait for the prefetched groups would wait for the load too) */
+        MZ_WAVE_SYNC();
+        MZ_LANES {
+            if (P(chs)) MZ_CHASE_LOAD_LEN(lp, P(tj), P(tt))
+        }
+#else
         MZ_LANES {
             if (P(chs)) { /* the window of lengths moves on: what was loaded four steps ago now, the next load from where the replay stands */
                 P(lw)[0] = P(lp)[0];
@@ -501,6 +614,7 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
             }
         }
         MZ_LANES { MZ_CHASE_REFILL(P(chs)) }
+#endif
         if (t2) MZ_CHASE_RETIRE_CHASE_TRIP(t2)
         MZ_LANES { P(lacc) = 0u; }
         MZ_WAVE_SYNC();
@@ -519,6 +633,12 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
             P(cfl) = 3u;
             P(chs) = 0u;
         }
+#if MZ_CHASE_LEAN
+        if (P(cfl) == 0u) { /* met: the target and its step have not moved since */
+            P(csx) = P(tj);
+            P(cst) = P(tt);
+        }
+#endif
     }
     if (t2) MZ_CHASE_RETIRE_CHASE_TRIP(t2)
     MZ_STAT(7, t2);
@@ -534,6 +654,9 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
 #undef MZ_CHASE_STORE_LEN
 #undef MZ_CHASE_REPLAY_ONE
 #undef MZ_CHASE_STEP
+#if MZ_CHASE_LEAN
+#undef MZ_CHASE_RETARGET
+#endif
 #undef MZ_CHASE_RETIRE_TRIP
 #undef MZ_CHASE_RETIRE_CHASE_TRIP
 #undef MZ_CHASE_STORE_QUAD
