@@ -240,6 +240,33 @@ MZHIP_API int32_t mzhip_bzip2_host(const uint8_t *in, uint32_t in_len, uint8_t *
  * and bytes of device scratch (the inverse-BWT arrays, per wave of the grid). */
 MZHIP_API void mzhip_bzip2_launch_geometry(uint32_t n, uint32_t *grid, uint64_t *scratch_bytes);
 
+/* Zstandard decode (ZIP method 93) with fused CRC-32 ------------------------------------ */
+
+/* Replaces, for n method-93 entries at once, mz_stream_zstd_read (mz_strm_zstd.c -> libzstd ZSTD_decompressStream) +
+ * mz_crypt_crc32_update (mz_zip.c:2049).  Signature and memory contract of mzhip_bzip2_batch: the input is read at BYTE
+ * granularity, never outside d_in + d_in_off[i] .. + d_in_len[i].  Entry i's input is what ZSTD_decompress takes: one or
+ * more frames of RFC 8878 back to back, skippable frames (magic 0x184D2A50 .. 0x184D2A5F) among them, and nothing else.
+ * One wave per entry; Frame_Content_Size and the content checksum (low 32 bits of XXH64) are verified on the device where
+ * a frame carries them.  Window_Size bounds the block size (min(Window_Size, 128 KiB)); a match distance is checked
+ * against the bytes the frame has produced, not against the window, as ZSTD_decompress does.
+ * Status: 0 every frame ended with its last block, every size and checksum present matched and the input was used up
+ * (d_in_used = d_in_len); -200 a block's bytes do not fit d_out_cap; -5 a field, a block body or a checksum would extend
+ * behind d_in_len (1 to 3 bytes where a magic number is due included), and d_in_len 0; -109 a frame whose Dictionary_ID is
+ * not 0; -3 everything else that is wrong (unknown magic, reserved bits or types, sizes over their maximum, incomplete or
+ * over-long Huffman codes, bad FSE tables, "repeat" with nothing to repeat, a bitstream without its final-bit marker or
+ * not consumed exactly, more literals asked for than exist, a distance before the frame's start, an offset of 0, a
+ * content size or checksum that does not match).  The first problem in stream order decides.  With a status other than 0,
+ * d_out_len counts the bytes of the complete blocks in front of the problem and d_crc is the CRC-32 of those. */
+MZHIP_API int32_t mzhip_zstd_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
+                                   const uint64_t *d_out_off, const uint32_t *d_out_cap, uint32_t n, uint32_t *d_out_len,
+                                   uint32_t *d_in_used, uint32_t *d_crc, int32_t *d_status, void *stream);
+/* one entry from a host buffer (H2D + kernel + D2H, synchronous), like mzhip_bzip2_host; returns the status */
+MZHIP_API int32_t mzhip_zstd_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, uint32_t *out_len,
+                                  uint32_t *in_used, uint32_t *crc);
+/* What a mzhip_zstd_batch launch of n entries would use: single-wave workgroups (min(n, resident waves of the device))
+ * and bytes of device scratch (a block's literals, per wave of the grid). */
+MZHIP_API void mzhip_zstd_launch_geometry(uint32_t n, uint32_t *grid, uint64_t *scratch_bytes);
+
 /* SHA-1 / SHA-224 / SHA-256 / SHA-384 / SHA-512 of n buffers ----------------------------- */
 
 /* What the reader's hash verification computes per entry on the CPU: mz_crypt_sha_begin/_update/_end over the

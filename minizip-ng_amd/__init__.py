@@ -212,6 +212,35 @@ def bzip2_host(data, out_cap):
     return int(st), int(iu.value), out.raw[: ol.value], int(crc.value)
 
 
+def zstd_batch(d_in, in_off, in_len, d_out, out_off, out_cap):
+    """ZIP method 93: the Zstandard frames of each entry through mzhip_zstd_batch on torch's current stream (asynchronous).
+    Tensors as for inflate_batch; returns CUDA tensors (out_len, in_used, crc, status)."""
+    import torch
+
+    require_gpu()
+    n = in_off.numel()
+    dev = d_in.device
+    out_len, in_used, crc, status = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
+    for t, dt in ((in_off, torch.int64), (out_off, torch.int64), (in_len, torch.int32), (out_cap, torch.int32)):
+        assert t.dtype == dt and t.is_cuda and t.is_contiguous()
+    assert d_in.dtype == torch.uint8 and d_out.dtype == torch.uint8
+    with torch.cuda.device(dev):
+        _check(lib().mzhip_zstd_batch(d_in.data_ptr(), in_off.data_ptr(), in_len.data_ptr(), d_out.data_ptr(),
+                                      out_off.data_ptr(), out_cap.data_ptr(), n, out_len.data_ptr(),
+                                      in_used.data_ptr(), crc.data_ptr(), status.data_ptr(), _stream_handle()),
+               "mzhip_zstd_batch")
+    return out_len, in_used, crc, status
+
+
+def zstd_host(data, out_cap):
+    """One entry's Zstandard frames through the host-buffer convenience entry point -> (status, in_used, out bytes, crc)."""
+    require_gpu()
+    out = C.create_string_buffer(max(out_cap, 1))
+    ol, iu, crc = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    st = lib().mzhip_zstd_host(bytes(data), len(data), out, out_cap, C.byref(ol), C.byref(iu), C.byref(crc))
+    return int(st), int(iu.value), out.raw[: ol.value], int(crc.value)
+
+
 def bzip2_encode_batch(d_in, in_off, in_len, d_out, out_off, out_cap, level=6):
     """ZIP method 12, the write side: one bzip2 stream per entry through mzhip_bzip2_encode_batch on torch's current stream
     (asynchronous).  Tensors as for inflate_batch; level 1..9 is the block-size digit, -1 the default 6.  The scratch is

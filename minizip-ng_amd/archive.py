@@ -3,7 +3,7 @@
 Host side of the "thousands of members in one launch" path (SURVEY 8b "Batching"): the central directory is
 indexed once by the C indexer (mzhip_zip_index_mem), the archive bytes are placed in HBM as they are (the entry
 payloads are used in place -- no repacking), and every entry of the shard is decoded by mzhip_inflate_batch /
-mzhip_bzip2_batch / mzhip_lzma_batch / mzhip_xz_batch / mzhip_crc32_batch according to its method.  The per-entry CRC is compared with
+mzhip_bzip2_batch / mzhip_zstd_batch / mzhip_lzma_batch / mzhip_xz_batch / mzhip_crc32_batch according to its method.  The per-entry CRC is compared with
 the central-directory CRC exactly where the reference compares it (mz_zip.c:2116-2128); with verify_hash the first
 Hash extrafield (0x1a51, doc/mz_extrafield.md) of each entry is checked against a device-computed SHA digest the way
 mz_zip_reader_entry_open / _close do it on the CPU in a crypto build (mz_zip_rw.c:409-451,465-466).
@@ -219,7 +219,8 @@ class DeviceArchive:
         """Decode entries [lo, hi).  Returns dict(crc u32[n], out_len i64[n], status i32[n], ok bool[n],
         out (uint8 CUDA tensor) , out_off i64[n]).  status: 0, MZ_* / zlib-numbered errors, MZ_CRC_ERROR when
         the CRC differs from the central directory, MZ_SUPPORT_ERROR for methods other than 0 (store) / 8 (DEFLATE) /
-        12 (bzip2) / 14 (LZMA) / 95 (xz) -- method 93 (zstd) among them -- and for a bzip2 block with the randomised bit.
+        12 (bzip2) / 14 (LZMA) / 93 (zstd) / 95 (xz), for a bzip2 block with the randomised bit and for a zstd frame that names
+        a dictionary.
         verify_hash: entries carrying a Hash extrafield are also checked against a device-computed SHA-1 / SHA-256
         (mismatch -> MZ_CRC_ERROR, other algorithms -> MZ_SUPPORT_ERROR, as mz_zip_reader_entry_open / _close).
         password (bytes): ZipCrypto and WinZip-AES entries are decrypted on the device into a scratch buffer (one call per
@@ -289,7 +290,7 @@ class DeviceArchive:
                         raise _mz.MzHipError("mzhip_inflate_large failed: %d %s" % (rc, L.mzhip_last_error().decode()))
                     crc[e], out_len[e] = ck.value, ol.value
                     status[e] = MZ_CRC_ERROR if (st1.value == 0 and iu.value == p_len[e] and not skip_crc[e] and ck.value != np.uint32(t[e, COL_CRC])) else st1.value
-                for method in (8, 12, 14, 95, 0):
+                for method in (8, 12, 93, 14, 95, 0):
                     sel = np.nonzero((meth == method) & from_here & ~((meth == 8) & (p_len >= LARGE_ENTRY)))[0]
                     if len(sel) == 0:
                         continue
@@ -299,8 +300,9 @@ class DeviceArchive:
                     d_in_off, d_in_len = dev_i64(p_off[sel]), dev_i32(p_len[sel])
                     d_out_off, d_cap = dev_i64(out_off[sel]), dev_i32(usize[sel])
                     r_len, r_used, r_crc, r_st = (torch.zeros(k, dtype=torch.int32, device=dev) for _ in range(4))
-                    if method in (8, 12):   # bzip2: one stream per entry, as BZ2_bzDecompress reads it (mz_strm_bzip.c)
-                        fn = L.mzhip_inflate_batch if method == 8 else L.mzhip_bzip2_batch
+                    if method in (8, 12, 93):   # bzip2: one stream per entry, as BZ2_bzDecompress reads it (mz_strm_bzip.c);
+                        # zstd: the entry's frames, as ZSTD_decompress reads them (mz_strm_zstd.c)
+                        fn = {8: L.mzhip_inflate_batch, 12: L.mzhip_bzip2_batch, 93: L.mzhip_zstd_batch}[method]
                         rc = fn(d_src.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(),
                                 d_out.data_ptr(), d_out_off.data_ptr(), d_cap.data_ptr(), k,
                                 r_len.data_ptr(), r_used.data_ptr(), r_crc.data_ptr(), r_st.data_ptr(),

@@ -391,6 +391,11 @@ int32_t mzhip_bzip2_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint3
     return decode_whole_host(MZ_LAUNCH_ONE(mzhip_bzip2_batch), in, in_len, out, out_cap, 0, out_len, in_used, crc, nullptr);
 }
 
+int32_t mzhip_zstd_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, uint32_t *out_len, uint32_t *in_used,
+                        uint32_t *crc) {
+    return decode_whole_host(MZ_LAUNCH_ONE(mzhip_zstd_batch), in, in_len, out, out_cap, 0, out_len, in_used, crc, nullptr);
+}
+
 // One ZIP method-14 payload from a host buffer.
 int32_t mzhip_lzma_encode_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, uint32_t *out_len,
                                uint32_t *crc) {

@@ -42,6 +42,7 @@
 #include "crypt_core.h"
 #include "bzip2_core.h"
 #include "bzip2_enc_core.h"
+#include "zstd_core.h"
 
 #ifndef MZ_WAVES_PER_WG
 #define MZ_WAVES_PER_WG 4
@@ -278,6 +279,49 @@ __global__ __launch_bounds__(64) void k_bzip2_batch(Bzip2Args a) {
         const uint8_t *in = a.in + MZ_UNIFORM64(io);
         uint8_t *out = a.out + MZ_UNIFORM64(oo);
         mz_bzip2_entry(in, MZ_UNIFORM(a.in_len[e]), out, MZ_UNIFORM(a.out_cap[e]), &lds, crc_tab, a.tabs, scratch, &r);
+        // wave-uniform results: stored by all lanes (same address, same value), see MZ_WAVE_FETCH_ADD
+        a.out_len[e] = r.out_len;
+        a.in_used[e] = r.in_used;
+        a.crc[e] = r.crc;
+        a.status[e] = r.status;
+    }
+}
+
+struct ZstdArgs {
+    const uint8_t *in;
+    const uint64_t *in_off;
+    const uint32_t *in_len;
+    uint8_t *out;
+    const uint64_t *out_off;
+    const uint32_t *out_cap;
+    uint32_t n;
+    uint32_t *out_len;
+    uint32_t *in_used;
+    uint32_t *crc;
+    int32_t *status;
+    uint32_t *counter;
+    const mzhip_crc_tables *tabs;
+    uint8_t *scratch; // MZ_ZS_SCRATCH_BYTES per wave of the grid: the literals of the block being decoded
+};
+
+// Zstandard (ZIP method 93): one wave per workgroup and per entry (zstd_core.h), 11.1 KiB of LDS (the Huffman and the three
+// FSE decode tables, the input window, the CRC byte table), persistent waves over a counter as in k_bzip2_batch.
+__global__ __launch_bounds__(64) void k_zstd_batch(ZstdArgs a) {
+    __shared__ __attribute__((aligned(16))) mz_zs_lds lds;
+    __shared__ uint32_t crc_tab[256];
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) crc_tab[i] = a.tabs->byte_tab[i];
+    __syncthreads();
+    MZ_LANE_DECL
+    uint8_t *const scratch = a.scratch + (size_t)blockIdx.x * MZ_ZS_SCRATCH_BYTES;
+    for (;;) {
+        uint32_t e;
+        MZ_WAVE_FETCH_ADD(e, a.counter);
+        if (e >= a.n) break;
+        mz_zs_result r;
+        const uint64_t io = a.in_off[e], oo = a.out_off[e];
+        const uint8_t *in = a.in + MZ_UNIFORM64(io);
+        uint8_t *out = a.out + MZ_UNIFORM64(oo);
+        mz_zstd_entry(in, MZ_UNIFORM(a.in_len[e]), out, MZ_UNIFORM(a.out_cap[e]), &lds, crc_tab, a.tabs, scratch, &r);
         // wave-uniform results: stored by all lanes (same address, same value), see MZ_WAVE_FETCH_ADD
         a.out_len[e] = r.out_len;
         a.in_used[e] = r.in_used;

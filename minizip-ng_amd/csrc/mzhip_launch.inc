@@ -405,6 +405,41 @@ int32_t mzhip_bzip2_batch(const void *d_in, const uint64_t *d_in_off, const uint
     return launched("k_bzip2_batch", hipGetLastError(), sc);
 }
 
+/* zstd: the literals of a block (at most 128 KiB) are decoded into HBM, MZ_ZS_SCRATCH_BYTES = 131 328 per resident wave.
+ * 8 single-wave workgroups per CU, two per SIMD, as for bzip2: the sequence machine is a chain of dependent LDS reads, so a
+ * wave mostly waits; LDS (11.1 KiB per wave) would allow 14.  A full grid on a 256-CU device holds 256 MiB of scratch.
+ * grid = min(n, resident). */
+#define MZ_ZS_WAVES_PER_CU 8u
+
+static uint32_t zstd_grid(const DeviceCtx *c, uint32_t n) { return resident_grid(n, (uint32_t)c->cu_count * MZ_ZS_WAVES_PER_CU); }
+
+void mzhip_zstd_launch_geometry(uint32_t n, uint32_t *grid, uint64_t *scratch_bytes) {
+    DeviceCtx *c = nullptr;
+    uint32_t g = 0;
+    if (ctx_for_current(&c) == 0) g = zstd_grid(c, n);
+    if (grid) *grid = g;
+    if (scratch_bytes) *scratch_bytes = (uint64_t)g * MZ_ZS_SCRATCH_BYTES;
+}
+
+int32_t mzhip_zstd_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
+                         const uint64_t *d_out_off, const uint32_t *d_out_cap, uint32_t n, uint32_t *d_out_len,
+                         uint32_t *d_in_used, uint32_t *d_crc, int32_t *d_status, void *stream) {
+    if (n == 0) return 0;
+    Launch L;
+    int32_t rc = L.begin(stream);
+    if (rc) return rc;
+    ZstdArgs a;
+    set_fields(a, L.c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, d_in_used, d_crc, d_status);
+    a.counter = L.head.p;
+    const uint32_t grid = zstd_grid(L.c, n);
+    ScratchLease sc;
+    rc = sc.get(&L.c->scratch, (size_t)grid * MZ_ZS_SCRATCH_BYTES, L.s);
+    if (rc) return rc;
+    a.scratch = (uint8_t *)sc.p;
+    hipLaunchKernelGGL(k_zstd_batch, dim3(grid), dim3(64), 0, L.s, a);
+    return launched("k_zstd_batch", hipGetLastError(), sc);
+}
+
 /* bzip2 encode: the sort of a block's rotations needs, per resident wave and per symbol the scratch holds, two rotation
  * orders and two rank arrays of 4 bytes each (prefix doubling reads one pair and writes the other; the second rank array
  * is the scatter's fill counts, the first holds the 16-bit symbols once the sort is done) and the symbol itself: 17 bytes,
