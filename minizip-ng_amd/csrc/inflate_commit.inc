@@ -108,12 +108,13 @@
             P(ca) = 0u;
             P(cb) = 0u;
         }
-#if MZ_NEAR_PACKED
-        /* The same two searches with ca and cb kept as BYTE offsets of the cross-lane gather (4 * rank: what ds_bpermute
-         * takes), so a step is add, gather, compare, add per query and nothing is shifted or masked on the way; the first
-         * step asks every lane for lane 31, which is a scalar read.  (One gather per step cannot serve both queries, packed
-         * keys or not: after the first step ca and cb of a lane stand at different ranks, and a gather hands a lane the
-         * register of ONE other lane.) */
+        /* The two searches keep ca and cb as BYTE offsets of the cross-lane gather (4 * rank: what ds_bpermute takes), so
+         * a step is add, gather, compare, add per query and nothing is shifted or masked on the way; the first step asks
+         * every lane for lane 31, which is a scalar read.  (One gather per step cannot serve both queries, packed keys or
+         * not: after the first step ca and cb of a lane stand at different ranks, and a gather hands a lane the register
+         * of ONE other lane.)
+         * (Ranks as lane indices, shifted and masked for every gather, and the prologue below by a division: 0.35 % slower,
+         * set-up loop 172 against 143 instructions: profiles/r10, DESIGN.md section 3 K1) */
         {
             PV(uint32_t, s0);
             PV(uint32_t, s1);
@@ -141,21 +142,6 @@
                 P(cb) >>= 2;
             }
         }
-#else
-#pragma unroll
-        for (uint32_t step = 32u; step != 0u; step >>= 1) {
-            PV(uint32_t, va);
-            PV(uint32_t, vb);
-            MZ_GATHER(va, ken, P(ca) + step - 1u);
-            MZ_GATHER(vb, kst, P(cb) + step - 1u);
-            MZ_LANES {
-                /* the part of the source that is not this piece's own output */
-                const uint32_t s0 = P(d0) - P(dist), s1 = s0 + ((P(rem) < P(dist)) ? P(rem) : P(dist));
-                if (P(va) <= s0) P(ca) += step;
-                if (P(vb) < s1) P(cb) += step;
-            }
-        }
-#endif
         MZ_LANES {
             /* (cb <= lane: a piece's source ends where its output starts at the latest) */
             P(dep) = (P(cb) > P(ca)) ? ((~0ull >> (64u - (P(cb) - P(ca)))) << P(ca)) : 0ull;
@@ -179,13 +165,10 @@
                     if (D < 8u) {
                         /* short period: byte by byte until a multiple of the period reaches 8, then the
                          * same 8-byte steps at that distance (every byte equals the one D' behind it) */
-#if MZ_NEAR_PACKED
-                        /* D8 - D for D = 1 .. 7 is 7, 6, 6, 4, 5, 6, 7 (D8 = 8, 8, 9, 8, 10, 12, 14): a nibble each of
-                         * one constant, where the line below divides by a variable (a reciprocal sequence on the device) */
+                        /* D8 = D * ((7 + D) / D), the first multiple of D from 8 on: D8 - D for D = 1 .. 7 is 7, 6, 6, 4, 5, 6, 7
+                         * (D8 = 8, 8, 9, 8, 10, 12, 14), a nibble each of one constant, where the quotient is a division by a
+                         * variable (a reciprocal sequence on the device) */
                         const uint32_t D8 = D + ((0x76546670u >> (4u * D)) & 15u);
-#else
-                        const uint32_t D8 = D * ((7u + D) / D);
-#endif
                         uint32_t pro = D8 - D;
                         if (pro > n) pro = n;
                         for (uint32_t k = 0; k < pro; k++) d[k] = d[(int32_t)k - (int32_t)D];

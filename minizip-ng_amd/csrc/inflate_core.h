@@ -103,12 +103,8 @@ extern __device__ unsigned long long mz_prof_buf[32];
 #define MZ_PRIO_AT(i) ((void)0)
 #endif
 
-#ifndef MZ_LROOT
 #define MZ_LROOT 8 /* literal/length fast-table index bits */
-#endif
-#ifndef MZ_DROOT
 #define MZ_DROOT 8 /* distance fast-table index bits        */
-#endif
 #define MZ_CROOT 7 /* code-length-code table bits (== max)  */
 /* ---- chase window: spans of up to MZ_CHASE_SMAX bits, one per lane; the stream reaches a lane through
  * its own ring of MZ_CRING_DW dwords in LDS (+ 2 that mirror the first two, so dword a, a + 1, a + 2 are one address),
@@ -131,29 +127,10 @@ extern __device__ unsigned long long mz_prof_buf[32];
                                                                      reads fall 7 - 11 %, its writes grow 40 - 60 %, the probe is 0.3 - 7 % slower: profiles/r5/call4_probe.log) */
 #define MZ_CRING_DW 16u /* a power of two: the slot of a stream dword is its index & 15, nothing to keep track of */
 #define MZ_CRING_RS 19u /* row stride: 16 + 2 mirrored, odd */
-#ifndef MZ_PF_GROUPS
-#define MZ_PF_GROUPS 2 /* groups of four stream dwords a lane loads at a time (inflate_walk.inc): 1 or 2 */
-#endif
-#ifndef MZ_WALK_EDGE_BRANCH
-#define MZ_WALK_EDGE_BRANCH 1 /* the walks' refill loads (inflate_walk.inc): 1 = a group inside the input is one 16-byte load and nothing
-                                 else, the two edge groups of a view sit in a branch of their own; 0 = selects in every lane (round 4 .. 8) */
-#endif
-#ifndef MZ_WALK_TRIP_REFILL
-#define MZ_WALK_TRIP_REFILL 1 /* 1 = one refill check per trip of four steps that hands over up to both prefetched groups, no
-                                 half-selects; 0 = a check every second step, one group per check (round 6 .. 8).  MZ_PF_GROUPS 2 only */
-#endif
-#if MZ_WALK_TRIP_REFILL && MZ_PF_GROUPS != 2
-#undef MZ_WALK_TRIP_REFILL
-#define MZ_WALK_TRIP_REFILL 0
-#endif
-#ifndef MZ_CHASE_LEAN
-#define MZ_CHASE_LEAN 1 /* pass 2 of the walks (inflate_walk.inc): 1 = a chase whose target lane's walk is over takes the next target at the
-                           top of the next trip, once per trip; 0 = inside each of the trip's four steps (round 4 .. 9) */
-#endif
-#ifndef MZ_NEAR_PACKED
-#define MZ_NEAR_PACKED 1 /* the near batches of the commit (inflate_commit.inc): 1 = the rank searches keep byte offsets for the gather
-                            and start with a scalar read, the short-period prologue takes its length from a packed constant;
-                            0 = shifted lane indices and a division by the distance (round 5 .. 9) */
+/* seven A/B knobs whose question is answered; a build that still names one would be the product under another name */
+#if defined(MZ_PF_GROUPS) || defined(MZ_WALK_TRIP_REFILL) || defined(MZ_WALK_EDGE_BRANCH) || defined(MZ_CHASE_LEAN) || \
+    defined(MZ_NEAR_PACKED) || defined(MZ_NEAR_TAIL) || defined(MZ_EMIT_PREFETCH)
+#error "MZ_PF_GROUPS, MZ_WALK_TRIP_REFILL, MZ_WALK_EDGE_BRANCH, MZ_CHASE_LEAN, MZ_NEAR_PACKED, MZ_NEAR_TAIL and MZ_EMIT_PREFETCH are closed and their losing code is deleted: see DESIGN.md, section 3 K1, for the measurements and the last commit that builds the other side"
 #endif
 #ifndef MZ_EMIT_GROUP
 #define MZ_EMIT_GROUP 8u /* records one lane turns into bytes per emit round (4 or 8: records are stored in quads) */
@@ -204,15 +181,7 @@ extern __device__ unsigned long long mz_prof_buf[32];
  * sum over root prefixes of 2^(longest code in the prefix - root), found by exhaustive dynamic programming over the
  * code-length counts (the same search as zlib's examples/enough.c; it reproduces zlib's 852 = 512 + 340 for a 9-bit
  * root and 592 = 64 + 528 for the 6-bit / 30-symbol distance case). */
-#if MZ_LROOT == 8
-#define MZ_LIT_SUB_ENTRIES 404
-#elif MZ_LROOT == 9
-#define MZ_LIT_SUB_ENTRIES 340
-#elif MZ_LROOT == 10
-#define MZ_LIT_SUB_ENTRIES 308
-#else
-#error "MZ_LROOT must be 8, 9 or 10"
-#endif
+#define MZ_LIT_SUB_ENTRIES 404 /* for the 8-bit root (MZ_LROOT) */
 
 MZ_DEV uint32_t mz_lit_ent(uint32_t s) {
     if (s < 256u) return 0x80u | (s << 16);
@@ -451,38 +420,9 @@ MZ_DEV void mz_copy32(uint8_t *dst, const uint8_t *src, uint32_t n) {
 }
 /* the same inside the staging area, where the source may end less than n (but at least 8) bytes in front of the
  * destination: 8-byte steps in order, each one reading only what the steps before it (or earlier pieces) wrote */
-#ifndef MZ_NEAR_TAIL
-#define MZ_NEAR_TAIL 0 /* 1: the last n & 7 bytes without a chain of 4-, 2- and 1-byte load -> store pairs (below).  Measured
-                          SLOWER: config 2 376.5 - 381.3 GiB/s against 382.9 - 385.7 (-1.5 %, profiles/r7; not profiled further --
-                          the kernel is short of issue slots, and this form has more exec brackets than the chain it replaces) */
-#endif
+/* (The last n & 7 bytes without the chain of 4-, 2- and 1-byte load -> store pairs -- one overlapping 8-byte pair, or the
+ * three loads before the three stores -- measured 1.5 % slower: profiles/r7) */
 MZ_DEV void mz_copy32_seq(uint8_t *dst, const uint8_t *src, uint32_t n) {
-#if MZ_NEAR_TAIL
-    /* The body steps stay in order.  The tail cannot alias itself: the distance is at least 8 and the tail at most 7 bytes.
-     *   n >= 8, n & 7 != 0: ONE 8-byte pair at offset n - 8 behind the body steps.  Its source ends at or before its own
-     *                       destination and lies below dst + n - 8, all of it written by the body steps or by earlier pieces;
-     *                       it writes the bytes in front of the tail once more with the values they hold.
-     *   n < 8:              source and destination do not overlap: the three loads first, then the three stores.
-     * The first 8-byte load and the small loads are all issued before the first store (the lanes of a round are one or the
-     * other). */
-    uint64_t v0 = 0;
-    uint32_t t4 = 0, t2 = 0, t1 = 0;
-    if (n >= 8u) v0 = mz_ld8(src);
-    if (n < 8u && (n & 4u)) t4 = mz_ld4(src);
-    if (n < 8u && (n & 2u)) t2 = mz_ld2(src + (n & 4u));
-    if (n < 8u && (n & 1u)) t1 = src[n - 1u];
-    if (n >= 8u) {
-        mz_st8(dst, v0);
-#pragma unroll
-        for (uint32_t k = 1; k < 4u; k++)
-            if (8u * k + 8u <= n) mz_st8(dst + 8u * k, mz_ld8(src + 8u * k));
-        if (n & 7u) mz_st8(dst + (n - 8u), mz_ld8(src + (n - 8u)));
-    } else {
-        if (n & 4u) mz_st4(dst, t4);
-        if (n & 2u) mz_st2(dst + (n & 4u), t2);
-        if (n & 1u) dst[n - 1u] = (uint8_t)t1;
-    }
-#else
     const uint32_t n8 = n & ~7u;
 #pragma unroll
     for (uint32_t k = 0; k < 4u; k++)
@@ -490,7 +430,6 @@ MZ_DEV void mz_copy32_seq(uint8_t *dst, const uint8_t *src, uint32_t n) {
     if (n & 4u) mz_st4(dst + n8, mz_ld4(src + n8));
     if (n & 2u) mz_st2(dst + n8 + (n & 4u), mz_ld2(src + n8 + (n & 4u)));
     if (n & 1u) dst[n - 1u] = src[n - 1u];
-#endif
 }
 
 /* One step of a chase-window walk (inflate_chase.inc) as its RECORD.  A DEFLATE token walk started at an arbitrary bit falls

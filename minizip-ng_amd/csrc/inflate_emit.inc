@@ -8,7 +8,9 @@
  * the entry's cursor, block and resume state.  Replaces, per window, the copy loops of zlib's inflate_fast() and the
  * mz_crypt_crc32_update behind mz_zip_entry_read (mz_zip.c:2049). */
 /* the lane's group of the round that starts at group G0_ of the chain: P(w)[] = its records (mz_chase_step), 0 where a slot is not the chain's; P(kq)[] = their bits | bytes the
- * token produces << 8, 0 = no record.  Expects tab_n / tab_e / tab_m / tab_g (LDS), Rp / Cp / Lp / Lc, NG. */
+ * token produces << 8, 0 = no record.  Expects tab_n / tab_e / tab_m / tab_g (LDS), Rp / Cp / Lp / Lc, NG.
+ * (The fetch half for the next round asked for as soon as this round's cut is known: 13 registers held across the commit, 40 -> 112 / 128
+ * bytes of scratch for 0.6 % with overlapping ranges: profiles/r7, DESIGN.md section 3 K1) */
 #define MZ_EMIT_LOAD_GROUP(G0_) \
         { \
             PV2(uint32_t, fw_, MZ_EMIT_GROUP); \
@@ -17,82 +19,71 @@
             PV(uint32_t, flo_); \
             PV(uint32_t, fhi_); \
             PV(uint32_t, fst_); \
-            MZ_EMIT_FETCH_GROUP(G0_, fw_, fk0_, fk1_, flo_, fhi_, fst_) \
-            MZ_EMIT_MASK_GROUP(fw_, fk0_, fk1_, flo_, fhi_, fst_) \
-        }
-/* the two halves of it.  FETCH: the search for the lane's group and the loads of its raw records (fw), step bytes (fk0, fk1)
- * and slot range (flo, fhi, fst) -- nothing a commit changes, so the next round's can be asked for while this round's bytes
- * are still on their way out (MZ_EMIT_PREFETCH).  MASK: P(w)[], P(kq)[] from them. */
-#define MZ_EMIT_FETCH_GROUP(G0_, fw, fk0, fk1, flo, fhi, fst) \
-        MZ_LANES { \
-            const uint32_t G = (G0_) + (uint32_t)lane; \
-            uint32_t lo = 0, hi_ = 0, st0 = 0; \
-            uint32_t kw0 = 0, kw1 = 0; \
+            /* the search for the lane's group and the loads of its raw records (fw_), step bytes (fk0_, fk1_) and slot range (flo_, fhi_, fst_) */ \
+            MZ_LANES { \
+                const uint32_t G = (G0_) + (uint32_t)lane; \
+                uint32_t lo = 0, hi_ = 0, st0 = 0; \
+                uint32_t kw0 = 0, kw1 = 0; \
 _Pragma("unroll") \
-            for (uint32_t k = 0; k < MZ_EMIT_GROUP; k++) P(fw)[k] = 0u; \
-            if (G < NG) { \
-                uint32_t j = 0; /* the first lane whose inclusive sum exceeds G */ \
+                for (uint32_t k = 0; k < MZ_EMIT_GROUP; k++) P(fw_)[k] = 0u; \
+                if (G < NG) { \
+                    uint32_t j = 0; /* the first lane whose inclusive sum exceeds G */ \
 _Pragma("unroll") \
-                for (uint32_t sp = 32u; sp; sp >>= 1) \
-                    if (tab_g[j + sp - 1u] <= G) j += sp; \
-                const uint32_t k = G - (j ? tab_g[j - 1u] : 0u); \
-                const uint32_t n = tab_n[j], e = tab_e[j], m = tab_m[j]; \
-                const uint32_t ts = e & 0x7FFFu; \
-                const uint32_t cr = (n > ts) ? ((n + MZ_EMIT_GROUP - 1u) / MZ_EMIT_GROUP) - ts / MZ_EMIT_GROUP : 0u; \
-                const uint8_t *base, *kbase; \
-                if (k < cr) { /* (a lane is always met at the START of one of its steps: no half records) */ \
-                    st0 = (ts / MZ_EMIT_GROUP + k) * MZ_EMIT_GROUP; \
-                    lo = (ts > st0) ? ts : st0; \
-                    hi_ = (n < st0 + MZ_EMIT_GROUP) ? n : st0 + MZ_EMIT_GROUP; \
-                    base = Rp; \
-                    kbase = Lp + j * MZ_REC_CAP1; \
-                } else { \
-                    st0 = (k - cr) * MZ_EMIT_GROUP; \
-                    lo = st0; \
-                    hi_ = (m < st0 + MZ_EMIT_GROUP) ? m : st0 + MZ_EMIT_GROUP; \
-                    base = Cp; \
-                    kbase = Lc + j * MZ_REC_CAP2; \
+                    for (uint32_t sp = 32u; sp; sp >>= 1) \
+                        if (tab_g[j + sp - 1u] <= G) j += sp; \
+                    const uint32_t k = G - (j ? tab_g[j - 1u] : 0u); \
+                    const uint32_t n = tab_n[j], e = tab_e[j], m = tab_m[j]; \
+                    const uint32_t ts = e & 0x7FFFu; \
+                    const uint32_t cr = (n > ts) ? ((n + MZ_EMIT_GROUP - 1u) / MZ_EMIT_GROUP) - ts / MZ_EMIT_GROUP : 0u; \
+                    const uint8_t *base, *kbase; \
+                    if (k < cr) { /* (a lane is always met at the START of one of its steps: no half records) */ \
+                        st0 = (ts / MZ_EMIT_GROUP + k) * MZ_EMIT_GROUP; \
+                        lo = (ts > st0) ? ts : st0; \
+                        hi_ = (n < st0 + MZ_EMIT_GROUP) ? n : st0 + MZ_EMIT_GROUP; \
+                        base = Rp; \
+                        kbase = Lp + j * MZ_REC_CAP1; \
+                    } else { \
+                        st0 = (k - cr) * MZ_EMIT_GROUP; \
+                        lo = st0; \
+                        hi_ = (m < st0 + MZ_EMIT_GROUP) ? m : st0 + MZ_EMIT_GROUP; \
+                        base = Cp; \
+                        kbase = Lc + j * MZ_REC_CAP2; \
+                    } \
+_Pragma("unroll") \
+                    for (uint32_t pp = 0; pp < MZ_EMIT_GROUP / 4u; pp++) { \
+                        mz_dw4 v; \
+                        __builtin_memcpy(&v, base + MZ_REC_ADDR(st0 / 4u + pp, j), 16); \
+                        P(fw_)[4u * pp] = v.v[0]; \
+                        P(fw_)[4u * pp + 1u] = v.v[1]; \
+                        P(fw_)[4u * pp + 2u] = v.v[2]; \
+                        P(fw_)[4u * pp + 3u] = v.v[3]; \
+                    } \
+                    { \
+                        const uint64_t kk = mz_ld8(kbase + st0); \
+                        kw0 = (uint32_t)kk; \
+                        kw1 = (uint32_t)(kk >> 32); \
+                    } \
                 } \
+                P(fk0_) = kw0; \
+                P(fk1_) = kw1; \
+                P(flo_) = lo; \
+                P(fhi_) = hi_; \
+                P(fst_) = st0; \
+            } \
+            /* P(w)[], P(kq)[] from them */ \
+            MZ_LANES { \
+                /* slots that are not the chain's hold nothing from here on */ \
 _Pragma("unroll") \
-                for (uint32_t pp = 0; pp < MZ_EMIT_GROUP / 4u; pp++) { \
-                    mz_dw4 v; \
-                    __builtin_memcpy(&v, base + MZ_REC_ADDR(st0 / 4u + pp, j), 16); \
-                    P(fw)[4u * pp] = v.v[0]; \
-                    P(fw)[4u * pp + 1u] = v.v[1]; \
-                    P(fw)[4u * pp + 2u] = v.v[2]; \
-                    P(fw)[4u * pp + 3u] = v.v[3]; \
-                } \
-                { \
-                    const uint64_t kk = mz_ld8(kbase + st0); \
-                    kw0 = (uint32_t)kk; \
-                    kw1 = (uint32_t)(kk >> 32); \
+                for (uint32_t r = 0; r < MZ_EMIT_GROUP; r++) { \
+                    const uint32_t st = P(fst_) + r; \
+                    const uint32_t kb = mz_bfe((r & 4u) ? P(fk1_) : P(fk0_), 8u * (r & 3u), 8); \
+                    const uint32_t in = (st >= P(flo_) && st < P(fhi_) && kb != 0u) ? 1u : 0u; \
+                    const uint32_t ln = (kb < MZ_K_LIT) ? mz_bfe(P(fw_)[r], 8, 8) + 3u : (kb < MZ_K_EOB) ? 1u : 0u; \
+                    P(w)[r] = in ? P(fw_)[r] : 0u; \
+                    P(kq)[r] = in ? ((kb & 63u) | (ln << 8)) : 0u; \
                 } \
             } \
-            P(fk0) = kw0; \
-            P(fk1) = kw1; \
-            P(flo) = lo; \
-            P(fhi) = hi_; \
-            P(fst) = st0; \
         }
-#define MZ_EMIT_MASK_GROUP(fw, fk0, fk1, flo, fhi, fst) \
-        MZ_LANES { \
-            /* slots that are not the chain's hold nothing from here on */ \
-_Pragma("unroll") \
-            for (uint32_t r = 0; r < MZ_EMIT_GROUP; r++) { \
-                const uint32_t st = P(fst) + r; \
-                const uint32_t kb = mz_bfe((r & 4u) ? P(fk1) : P(fk0), 8u * (r & 3u), 8); \
-                const uint32_t in = (st >= P(flo) && st < P(fhi) && kb != 0u) ? 1u : 0u; \
-                const uint32_t ln = (kb < MZ_K_LIT) ? mz_bfe(P(fw)[r], 8, 8) + 3u : (kb < MZ_K_EOB) ? 1u : 0u; \
-                P(w)[r] = in ? P(fw)[r] : 0u; \
-                P(kq)[r] = in ? ((kb & 63u) | (ln << 8)) : 0u; \
-            } \
-        }
-#ifndef MZ_EMIT_PREFETCH
-#define MZ_EMIT_PREFETCH 0 /* 1: the next round's records are asked for as soon as this round's cut is known (mz_chase_emit).
-                              Off: the 13 registers it holds across the commit take k_inflate_batch from 40 to 112 / 128 bytes of
-                              scratch, and config 2 gains 0.6 % (385.0 - 388.6 GiB/s against 382.9 - 385.7: the ranges overlap;
-                              profiles/r7) */
-#endif
 
 typedef struct mz_emit_result {
     uint32_t out_pos, crc_done;
@@ -129,27 +120,12 @@ MZ_DEV_NOINLINE mz_emit_result mz_chase_emit(mz_lds_handle L_, uint32_t sub_used
     uint32_t cbits = 0;         /* bits of the records committed so far */
     uint32_t fail = 0;
     PV(uint32_t, bad);
-#if MZ_EMIT_PREFETCH
-    /* the round's group, asked for one round ahead: the search (six dependent LDS steps) and the record loads (usually a
-     * trip to memory) run under the round before instead of in front of this one; a round that fails drops them */
-    PV2(uint32_t, nw, MZ_EMIT_GROUP);
-    PV(uint32_t, nk0);
-    PV(uint32_t, nk1);
-    PV(uint32_t, nlo);
-    PV(uint32_t, nhi);
-    PV(uint32_t, nst);
-    MZ_EMIT_FETCH_GROUP(G0, nw, nk0, nk1, nlo, nhi, nst)
-#endif
     while (G0 < NG) {
         MZ_STAT(9, 1);
         const uint32_t sb = (uint32_t)((uintptr_t)(out + out_pos) & 15u);
         PV2(uint32_t, w, MZ_EMIT_GROUP);  /* the lane's records (mz_chase_step), 0 where the slot is not the chain's */
         PV2(uint32_t, kq, MZ_EMIT_GROUP); /* ... their bits | bytes the token produces << 8; 0 = no record */
-#if MZ_EMIT_PREFETCH
-        MZ_EMIT_MASK_GROUP(nw, nk0, nk1, nlo, nhi, nst)
-#else
         MZ_EMIT_LOAD_GROUP(G0)
-#endif
         /* what the lane's records produce: bytes, pieces, bits */
 #define MZ_CHASE_REC(r_, in_, rc_, ln_)                                                      \
         const uint32_t rc_ = P(w)[(r_)];                                                     \
@@ -185,9 +161,6 @@ MZ_DEV_NOINLINE mz_emit_result mz_chase_emit(mz_lds_handle L_, uint32_t sub_used
          * 72 pieces are 2.7 KB of the >= 5 KB a pool has).  Round 4 let the cut lane take a prefix of its records, counted
          * once more record by record in every lane on every round: ~100 instructions a round to fill the pool's last 26 bytes */
         const uint32_t cut = nofit ? mz_ctz64(nofit) : 64u;
-#if MZ_EMIT_PREFETCH
-        MZ_EMIT_FETCH_GROUP(G0 + cut, nw, nk0, nk1, nlo, nhi, nst) /* the next round starts here (nothing is loaded past the chain's end) */
-#endif
         PV(uint32_t, acc); /* record slots of this lane that are taken */
         uint32_t Tb, Tm, Tbits;
         MZ_LANES {

@@ -55,8 +55,8 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
      * eight wave-uniform values (`ev`, lanes 0 .. 7: MZ_EDGE_GROUPS of mz_inflate_entry loads them once per view; scalar
      * registers here), masked as mz_load_stream_dword masks them.  MZ_CHASE_LOAD_DW4, the initial fill of a ring in front
      * of the loops, is ONE global load for every lane -- from a harmless interior address where the group is an edge --
-     * and eight selects; the refills inside the two loops go through MZ_CHASE_RELOAD_DW4 below, which was the same until
-     * round 9 and is a plain load with the edges in a branch since.  (The r3 refill
+     * and eight selects; the refills inside the two loops go through MZ_CHASE_RELOAD_DW4 below, a plain load with the
+     * edges in a branch.  (The r3 refill
      * carried four masked loads with 64-bit address arithmetic, ~100 instructions and a dozen registers, through both walk
      * loops; a copy of the edge groups in LDS turns the load into a flat one -- a select between a global and an LDS
      * pointer -- and a copy in global scratch costs every window a store, a fence and a round trip before its first load:
@@ -80,18 +80,17 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         P(dst)[(o_) + 2] = int_ ? v_.v[2] : z_ ? e0[2] : l_ ? el[2] : 0u;                    \
         P(dst)[(o_) + 3] = int_ ? v_.v[3] : z_ ? e0[3] : l_ ? el[3] : 0u;                    \
     }
-    /* The same for the refills inside the two walk loops, where the selects above were ~50 of the ~70 vector instructions of
-     * a check that runs in every wave at every check, for two groups per view that almost no lane ever loads
-     * (MZ_WALK_EDGE_BRANCH 1).  A lane whose group lies inside the input does its one 16-byte load and nothing else; a lane
-     * whose group does not loads nothing -- no byte outside the aligned dwords of [in, in + in_len) is touched, and none
-     * from a stand-in address either -- and takes its values from `el` or zeros in a branch of its own, which the wave
-     * jumps over when no lane is there.
+    /* The same for the refills inside the two walk loops, without the selects.  A lane whose group lies inside the input
+     * does its one 16-byte load and nothing else; a lane whose group does not loads nothing -- no byte outside the aligned
+     * dwords of [in, in + in_len) is touched, and none from a stand-in address either -- and takes its values from `el` or
+     * zeros in a branch of its own, which the wave jumps over when no lane is there.
      *   The group of dword 0 cannot occur here: a lane starts with hi = (first dword & ~3) + MZ_CRING_DW >= 16, hi only
      * grows, and a refill loads the groups at hi and hi + 4 >= 16.  So every d_ is above dw_lo (which is 0 or 1), `e0` is
      * never looked at, and "inside the input" is d_ + 4 <= dw_hi alone.  What is left of the edges: d_ == gl4, the
      * group with the last (partial) dword, already masked in `el`; and d_ > gl4, zeros.  (gl4 + 4 > dw_hi always, so the
-     * three cases do not overlap.) */
-#if MZ_WALK_EDGE_BRANCH
+     * three cases do not overlap.)
+     * (Selects instead of the branch, MZ_CHASE_LOAD_DW4 in the refills too: ~50 of a check's ~70 vector instructions in
+     * every wave at every check, the branch alone measured +5.4 % on 64 KiB entries: profiles/r9, DESIGN.md section 3 K1) */
 #define MZ_CHASE_RELOAD_DW4(dst, o_, d_)                                                     \
     {                                                                                        \
         const uint32_t dd_ = (d_); /* a multiple of 4, >= MZ_CRING_DW */                     \
@@ -110,22 +109,17 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
             P(dst)[(o_) + 3] = l_ ? el[3] : 0u;                                              \
         }                                                                                    \
     }
-#else
-#define MZ_CHASE_RELOAD_DW4(dst, o_, d_) MZ_CHASE_LOAD_DW4(dst, o_, d_)
-#endif
 
     PV(uint32_t, lim); /* where its span ends */
     PV(uint32_t, hi);  /* next stream dword the ring takes ... */
     PV(uint32_t, hs);  /* ... and the slot it goes to (0, 4, 8, 12) */
     /* The stream reaches a lane 16 bytes at a time, and 64 lanes stand in 64 different cache lines: a line was fetched eight
      * times over its sixteen steps, almost always from the fabric (the streams of the waves of an XCD do not fit its L2 --
-     * round 5: refills + records were 46 % of K1's fabric reads).  MZ_PF_GROUPS = 2: the NEXT TWO groups are loaded together,
-     * two 16-byte loads of one instruction pair into the same line, every second refill: half the line fetches for four
-     * selects per refill (profiles/r6/ab_k1_pf.log). */
-    PV2(uint32_t, pf, 4 * MZ_PF_GROUPS); /* dwords hi .. hi + 3 (and hi + 4 .. hi + 7), loaded at an earlier check */
-#if MZ_PF_GROUPS == 2
-    PV(uint32_t, ph); /* which half of pf is next */
-#endif
+     * round 5: refills + records were 46 % of K1's fabric reads).  So the NEXT TWO groups are loaded together, two 16-byte
+     * loads of one instruction pair into the same line: half the line fetches.
+     * (One group per load: 3.7 % more bytes read for the same time, profiles/r6/ab_k1_pf.log, DESIGN.md section 3 K1) */
+    PV2(uint32_t, pf, 8); /* dwords hi .. hi + 3 and hi + 4 .. hi + 7, loaded at an earlier check */
+    PV(uint32_t, ph);     /* 1: the first group has gone to the ring, pf[0 .. 3] holds the second */
     PV(uint32_t, run);
     PV2(uint32_t, rb, 4); /* the records of the current trip's four steps */
     PV(uint32_t *, row);
@@ -140,10 +134,8 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         P(hs) = (P(u) >> 5) & (MZ_CRING_DW - 1u) & ~3u; /* stream dword d lives in slot d & 15: the first refill goes where the span's first four dwords are */
         P(hi) = ((P(u) >> 5) & ~3u) + MZ_CRING_DW;
         P(pf)[0] = P(pf)[1] = P(pf)[2] = P(pf)[3] = 0u;
-#if MZ_PF_GROUPS == 2
         P(pf)[4] = P(pf)[5] = P(pf)[6] = P(pf)[7] = 0u;
         P(ph) = 0u;
-#endif
         P(rb)[0] = P(rb)[1] = P(rb)[2] = P(rb)[3] = 0u;
         if (P(run)) {
             const uint32_t a0 = (P(u) >> 5) & ~3u; /* the ring is filled and topped up in aligned groups of four dwords */
@@ -162,16 +154,13 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
                 }
             }
             MZ_CHASE_LOAD_DW4(pf, 0, P(hi))
-#if MZ_PF_GROUPS == 2
             MZ_CHASE_LOAD_DW4(pf, 4, P(hi) + 4u)
-#endif
         }
     }
     MZ_WAVE_SYNC();
 
-#if MZ_WALK_TRIP_REFILL
-    /* ONE refill check per trip of four steps (MZ_WALK_TRIP_REFILL 1; MZ_CRING_DW is 16).  Write c = u >> 5 for the dword
-     * the cursor stands in and gap = hi - c for the dwords of the ring from there on (the ring holds dwords hi - 16 .. hi - 1).
+    /* ONE refill check per trip of four steps (MZ_CRING_DW is 16).  Write c = u >> 5 for the dword the cursor stands in
+     * and gap = hi - c for the dwords of the ring from there on (the ring holds dwords hi - 16 .. hi - 1).
      * The four slots at hs hold dwords hi - 16 .. hi - 13: dead when c >= hi - 12, gap <= 12; the four behind them too when
      * gap <= 8.  The check hands over
      *     both prefetched groups   when gap <= 8 and both are there (ph == 0),     gap' = gap + 8,
@@ -188,9 +177,10 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
      *   trip's last step starts at most 189 bits in, c has moved by at most (31 + 189) >> 5 = 6, and c + 6 + 2 < c + 9 <= hi:
      *   every dword a step looks at is in the ring (none older than hi - 16 either: gap' <= 16 because nothing is handed
      *   over above gap 12 and two groups only up to gap 8).  The bound is tight, so the ring cannot be smaller.
-     * pf[0 .. 3] is always the next group: when one group goes, the other moves down (four copies in that branch only,
-     * where round 6 .. 8 picked a half with eight selects at every check), and the two groups of a line are still asked
-     * for together, when both have gone. */
+     * pf[0 .. 3] is always the next group: when one group goes, the other moves down (four copies in that branch only),
+     * and the two groups of a line are still asked for together, when both have gone.
+     * (A check every second step that hands over one group, picked with eight selects: the trip's one check alone measured
+     * +3.5 % on 64 KiB entries, profiles/r9, DESIGN.md section 3 K1) */
 /* (Reloading the prefetch registers in every lane at every check -- no merge copies, 13 vector instructions fewer per trip --
  * measured 5 % slower on 64 KiB entries: profiles/r5/call21_probe.log, call22) */
 #define MZ_CHASE_REFILL_PUT(o_)                                                              \
@@ -227,52 +217,6 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
             }                                                                                \
         }                                                                                    \
     }
-#elif MZ_PF_GROUPS == 2
-    /* the ring takes the prefetched dwords as soon as their slots are dead (they hold dwords hi - 16 .. hi - 13: the cursor
-     * has passed them when it is within 12 dwords of hi); two steps eat at most 126 bits, so checking every second step
-     * keeps nine dwords ahead of any cursor, and a step looks at three */
-#define MZ_CHASE_REFILL(active_)                                                             \
-    if (active_) {                                                                           \
-        if (P(hi) - (P(u) >> 5) <= MZ_CRING_DW - 4u) {                                       \
-            uint32_t *const w_ = P(row) + P(hs);                                             \
-            const uint32_t s_ = P(ph);                                                       \
-            const uint32_t p0_ = s_ ? P(pf)[4] : P(pf)[0], p1_ = s_ ? P(pf)[5] : P(pf)[1];   \
-            w_[0] = p0_;                                                                     \
-            w_[1] = p1_;                                                                     \
-            w_[2] = s_ ? P(pf)[6] : P(pf)[2];                                                \
-            w_[3] = s_ ? P(pf)[7] : P(pf)[3];                                                \
-            if (P(hs) == 0u) {                                                               \
-                P(row)[MZ_CRING_DW] = p0_;                                                   \
-                P(row)[MZ_CRING_DW + 1u] = p1_;                                              \
-            }                                                                                \
-            P(hs) = (P(hs) + 4u) & (MZ_CRING_DW - 1u);                                       \
-            P(hi) += 4u;                                                                     \
-            P(ph) = s_ ^ 1u;                                                                 \
-            if (s_) { /* both halves are in the ring: the next two groups, one line */       \
-                MZ_CHASE_RELOAD_DW4(pf, 0, P(hi))                                              \
-                MZ_CHASE_RELOAD_DW4(pf, 4, P(hi) + 4u)                                         \
-            }                                                                                \
-        }                                                                                    \
-    }
-#else
-#define MZ_CHASE_REFILL(active_)                                                             \
-    if (active_) {                                                                           \
-        if (P(hi) - (P(u) >> 5) <= MZ_CRING_DW - 4u) {                                       \
-            uint32_t *const w_ = P(row) + P(hs);                                             \
-            w_[0] = P(pf)[0];                                                                \
-            w_[1] = P(pf)[1];                                                                \
-            w_[2] = P(pf)[2];                                                                \
-            w_[3] = P(pf)[3];                                                                \
-            if (P(hs) == 0u) {                                                               \
-                P(row)[MZ_CRING_DW] = P(pf)[0];                                              \
-                P(row)[MZ_CRING_DW + 1u] = P(pf)[1];                                         \
-            }                                                                                \
-            P(hs) = (P(hs) + 4u) & (MZ_CRING_DW - 1u);                                       \
-            P(hi) += 4u;                                                                     \
-            MZ_CHASE_RELOAD_DW4(pf, 0, P(hi))                                                  \
-        }                                                                                    \
-    }
-#endif
 #define MZ_CHASE_ST16(p_, v_) __builtin_memcpy((p_), &(v_), 16);
 #define MZ_CHASE_STORE_QUAD(base_, quad_)                                                    \
     if (P(lacc) != 0u) { /* (a lane that took no step in the trip has nothing to say: nobody reads behind its last record) */ \
@@ -302,19 +246,10 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         P(sfl) = kk_; /* the last step's K byte: how the walk ended is read off it behind the loop */ \
         P(run) = (((kk_ - 1u) < 0x7Fu) & (nu_ < P(lim))) ? 1u : 0u;                          \
     }
-    /* two steps (behind a refill check of their own where MZ_WALK_TRIP_REFILL is 0); the first pair of a trip also sends the quad of the trip before (issued with the \
-     * loads, waited for with them) */
-#if MZ_WALK_TRIP_REFILL
+    /* two steps */
 #define MZ_CHASE_OWN_PAIR(B) /* (the trip's one check stands at its top) */                  \
     MZ_LANES { MZ_CHASE_OWN_STEP(B) }                                                        \
     MZ_LANES { MZ_CHASE_OWN_STEP((B) + 1) }
-#else
-#define MZ_CHASE_OWN_PAIR(B)                                                                 \
-    MZ_LANES { MZ_CHASE_REFILL(P(run)) }                                                     \
-    MZ_WAVE_SYNC();                                                                          \
-    MZ_LANES { MZ_CHASE_OWN_STEP(B) }                                                        \
-    MZ_LANES { MZ_CHASE_OWN_STEP((B) + 1) }
-#endif
 #define MZ_CHASE_STORE_LEN(base_, cap_, row_)                                                \
     {                                                                                        \
         mz_dw4 v_;                                                                           \
@@ -403,9 +338,8 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         P(dst)[2] = v_.v[2];                                                                 \
         P(dst)[3] = v_.v[3];                                                                 \
     }
-#if MZ_CHASE_LEAN
-    /* (MZ_CHASE_LEAN 1: a target is taken in front of a trip only, where the window of lengths moves on anyway -- its first
-     * sixteen lengths are asked for as the load in flight, and the renewal right behind hands them over) */
+    /* (a target is taken in front of a trip only, where the window of lengths moves on anyway -- its first sixteen lengths
+     * are asked for as the load in flight, and the renewal right behind hands them over) */
 #define MZ_CHASE_TARGET(lane_)                                                               \
     {                                                                                        \
         P(tt) = 0u;                                                                          \
@@ -414,21 +348,6 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         P(pb) = 0u;                                                                          \
         MZ_CHASE_LOAD_LEN(lp, (lane_), 0u)                                                   \
     }
-#else
-#define MZ_CHASE_TARGET(lane_)                                                               \
-    {                                                                                        \
-        P(tt) = 0u;                                                                          \
-        P(uo) = Wu + (lane_) * S;                                                            \
-        P(tn) = tab_walk[(lane_)];                                                           \
-        P(lb) = 0u;                                                                          \
-        P(pb) = 0u;                                                                          \
-        MZ_CHASE_LOAD_LEN(lw, (lane_), 0u)                                                   \
-        P(lp)[0] = P(lw)[0];                                                                 \
-        P(lp)[1] = P(lw)[1];                                                                 \
-        P(lp)[2] = P(lw)[2];                                                                 \
-        P(lp)[3] = P(lw)[3];                                                                 \
-    }
-#endif
     MZ_LANES {
         P(chs) = ((uint32_t)lane + 1u < nact && P(sfl) == 0u) ? 1u : 0u;
         P(cm) = 0u;
@@ -454,10 +373,9 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         P(uo) += mz_bfe((ix_ & 8u) ? wb_ : wa_, 8u * (ix_ & 3u), 6); /* (the K byte's low six bits) */ \
         P(tt)++;                                                                             \
     }
-#if MZ_CHASE_LEAN
-    /* MZ_CHASE_LEAN 1: a step only ever STOPS a chase -- at a meeting point, an end of block, an invalid code -- and says how
-     * in cfl; it takes no new target (MZ_CHASE_RETARGET, in front of the trip) and copies nothing: a lane that has stopped
-     * replays no more, so tj and tt stay what they were at the meeting point and are read off behind the loop. */
+    /* A step only ever STOPS a chase -- at a meeting point, an end of block, an invalid code -- and says how in cfl; it
+     * takes no new target (MZ_CHASE_RETARGET, in front of the trip) and copies nothing: a lane that has stopped replays no
+     * more, so tj and tt stay what they were at the meeting point and are read off behind the loop. */
 #define MZ_CHASE_STEP(K)                                                                     \
     MZ_CHASE_REPLAY_ONE                                                                      \
     MZ_CHASE_REPLAY_ONE                                                                      \
@@ -497,73 +415,33 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
             }                                                                                \
         }                                                                                    \
     }
-#else
-#define MZ_CHASE_STEP(K)                                                                     \
-    MZ_CHASE_REPLAY_ONE                                                                      \
-    MZ_CHASE_REPLAY_ONE                                                                      \
-    if (P(chs)) {                                                                            \
-        const uint32_t on_ = P(tn) & 0xFFFFu, of_ = P(tn) >> 16;                             \
-        if (P(uo) == P(u) && (P(tt) < on_ || of_ == 0u)) {                                   \
-            /* the start of a step of that lane's walk (or the very place it crossed): its records go on from here */ \
-            P(cfl) = 0u;                                                                     \
-            P(csx) = P(tj);                                                                  \
-            P(cst) = P(tt);                                                                  \
-            P(chs) = 0u;                                                                     \
-        } else if (P(tt) >= on_ && P(uo) <= P(u)) {                                          \
-            /* that lane's walk is over (it crossed behind us, or stopped for a reason of its own): on to the next span */ \
-            P(tj)++;                                                                         \
-            MZ_STAT(27, 1);                                                                  \
-            if (P(tj) >= nact) {                                                             \
-                P(cfl) = 4u;                                                                 \
-                P(chs) = 0u;                                                                 \
-            } else {                                                                         \
-                MZ_CHASE_TARGET(P(tj))                                                       \
-            }                                                                                \
-        }                                                                                    \
-    }                                                                                        \
-    if (P(chs)) {                                                                            \
-        const uint32_t *const rp_ = P(row) + ((P(u) >> 5) & (MZ_CRING_DW - 1u));             \
-        uint32_t r_;                                                                         \
-        const uint32_t k_ = mz_chase_step(L, rp_[0], rp_[1], rp_[2], P(u), 64u, &r_);        \
-        const uint32_t ok_ = ((k_ & 63u) != 0u && P(u) + (k_ & 63u) <= Eu) ? 1u : 0u;        \
-        const uint32_t kk_ = ok_ ? k_ : 0u;                                                  \
-        P(rb)[(K)] = r_;                                                                     \
-        P(lacc) |= kk_ << (8 * (K));                                                         \
-        P(cm) += ok_;                                                                        \
-        P(u) += kk_ & 63u;                                                                   \
-        if (!ok_ || (k_ & MZ_K_EOB)) {                                                       \
-            P(cfl) = ok_ ? 1u : 2u;                                                          \
-            P(chs) = 0u;                                                                     \
-        }                                                                                    \
-    }
-#endif
     /* the trip before: its quad of records and its four K bytes (one dword into the lane's row of the chases' K stream) */
 #define MZ_CHASE_RETIRE_CHASE_TRIP(t_)                                                       \
     MZ_LANES {                                                                               \
         MZ_CHASE_STORE_QUAD(Cp, ((t_) - 4u) >> 2)                                            \
         if (P(lacc) != 0u) mz_st4(Lc + ((uint32_t)lane * MZ_REC_CAP2 + ((t_) - 4u)), P(lacc)); \
     }
-    /* MZ_CHASE_LEAN 1 -- ONE place per trip where a chase takes a new target, in front of the trip, where rounds 4 .. 9 had one
-     * in each of the four steps (a table read, a 16-byte load with its wait, and the copies that keep tj, tt, uo, csx, cst and
-     * cfl apart on every way through a step: ~18 register copies per step in every wave, retarget or not).
-     * WHAT CHANGES: only WHEN a lane starts to replay its next target -- up to three steps later.  WHAT DOES NOT: what the
-     * lane decodes.  A chasing lane decodes one step per step of the trip in either build, with or without a target to
-     * replay (the old step retargets and decodes on in the same step), so u after k steps, the records rb / lacc, their
+    /* ONE place per trip where a chase takes a new target, in front of the trip, and not one in each of its four steps.
+     * (A retarget in every step -- a table read, a 16-byte load with its wait and ~18 register copies per step in every wave,
+     * retarget or not -- measured 1.4 % slower on 64 KiB entries: profiles/r10, DESIGN.md section 3 K1)
+     * WHAT CHANGES against a retarget in the step where the target ran out: only WHEN a lane starts to replay its next
+     * target -- up to three steps later.  WHAT DOES NOT: what the lane decodes.  A chasing lane decodes one step per step of
+     * the trip, with or without a target to replay, so u after k steps, the records rb / lacc, their
      * slots (step t2 + K of the chase is record t2 + K: no step is left out, so there are no holes in the quads or in the K
      * stream), cm, and an end of block or invalid code with its cfl = 1 / 2 are the same step for step.  A lane that idled
      * until the next trip instead would leave such holes; it must not.
      * PROOF that the result of the window is a true parse all the same.  The chain (inflate_chase.inc) asks of a chase
      * only this: cfl == 0 means that after cm recorded steps the cursor u stands where step cst of lane csx's own walk
      * starts (or, cst == sn of a lane that crossed, where that walk ended); cfl != 0 means that after cm recorded steps the
-     * cursor is u, and why it stopped.  A step sets cfl = 0 under the very condition of rounds 4 .. 9 -- uo == u with uo the
+     * cursor is u, and why it stopped.  A step sets cfl = 0 under one condition only -- uo == u with uo the
      * sum of the first tt lengths of lane tj's walk from its span's start, tt < on or the walk crossed -- and csx / cst are tj
      * / tt of that moment, because a lane that stopped replays no more and takes no target (both ask for chs); they are
      * read off behind the loop.  So every meeting point reported is one.  It may be a LATER one of the same two walks than
-     * before, or one with a later lane; the chain then follows this lane's records (the same tokens: two walks that stand
+     * an immediate retarget would find, or one with a later lane; the chain then follows this lane's records (the same tokens: two walks that stand
      * on one token start decode the same from there) for longer before it changes over.  Leaving the window (tj reaches
      * nact) is noticed up to three steps later: cm and u are those steps further on, valid steps each (ok_ asks for
      * every one to end inside the input), and the next window starts there.  The record cap: a chase still running at
-     * t2 == MZ_REC_CAP2 gets cfl = 3 as before, now possibly one that would have met in its last steps; the chain ends
+     * t2 == MZ_REC_CAP2 gets cfl = 3, possibly one that an immediate retarget would have let meet in its last steps; the chain ends
      * there and the next window goes on from u with shorter spans -- slower, never different bytes.
      *   A target that is over but IS a meeting point (uo == u, the walk crossed, tt == on) is left for step 0 to report: the
      * retarget asks for uo < u, or uo == u behind a walk that stopped for a reason of its own.
@@ -573,13 +451,10 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
      * tt = 0) and asks again: no copy of the window outside the renewal. */
     uint32_t t2 = 0;
     for (;;) {
-#if MZ_CHASE_LEAN
         MZ_LANES { MZ_CHASE_RETARGET }
-#endif
         uint64_t live;
         MZ_BALLOT(live, P(chs) != 0u);
         if (!live || t2 >= MZ_REC_CAP2) break;
-#if MZ_CHASE_LEAN
         /* the same renewal in two halves with the compiler's memory barrier between them: the load is to go straight into
          * lp's registers, which are free once lw has taken their values.  (In one piece the load was issued first, into
          * registers of its own, and waited for on the spot to be copied into lp: the prefetch hid nothing.) */
@@ -601,29 +476,11 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
         MZ_LANES {
             if (P(chs)) MZ_CHASE_LOAD_LEN(lp, P(tj), P(tt))
         }
-#else
-        MZ_LANES {
-            if (P(chs)) { /* the window of lengths moves on: what was loaded four steps ago now, the next load from where the replay stands */
-                P(lw)[0] = P(lp)[0];
-                P(lw)[1] = P(lp)[1];
-                P(lw)[2] = P(lp)[2];
-                P(lw)[3] = P(lp)[3];
-                P(lb) = P(pb);
-                P(pb) = P(tt);
-                MZ_CHASE_LOAD_LEN(lp, P(tj), P(tt))
-            }
-        }
-        MZ_LANES { MZ_CHASE_REFILL(P(chs)) }
-#endif
         if (t2) MZ_CHASE_RETIRE_CHASE_TRIP(t2)
         MZ_LANES { P(lacc) = 0u; }
         MZ_WAVE_SYNC();
         MZ_LANES { MZ_CHASE_STEP(0) }
         MZ_LANES { MZ_CHASE_STEP(1) }
-#if !MZ_WALK_TRIP_REFILL
-        MZ_LANES { MZ_CHASE_REFILL(P(chs)) }
-        MZ_WAVE_SYNC();
-#endif
         MZ_LANES { MZ_CHASE_STEP(2) }
         MZ_LANES { MZ_CHASE_STEP(3) }
         t2 += 4u;
@@ -633,12 +490,10 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
             P(cfl) = 3u;
             P(chs) = 0u;
         }
-#if MZ_CHASE_LEAN
         if (P(cfl) == 0u) { /* met: the target and its step have not moved since */
             P(csx) = P(tj);
             P(cst) = P(tt);
         }
-#endif
     }
     if (t2) MZ_CHASE_RETIRE_CHASE_TRIP(t2)
     MZ_STAT(7, t2);
@@ -646,17 +501,13 @@ MZ_DEV_NOINLINE mz_walk_result mz_chase_walk(mz_lds_handle L_, mz_glb_handle in_
     MZ_CHASE_FENCE();
     MZ_PROF_MARK(5); /* pass 2 */
 #undef MZ_CHASE_REFILL
-#if MZ_WALK_TRIP_REFILL
 #undef MZ_CHASE_REFILL_PUT
-#endif
 #undef MZ_CHASE_OWN_STEP
 #undef MZ_CHASE_OWN_PAIR
 #undef MZ_CHASE_STORE_LEN
 #undef MZ_CHASE_REPLAY_ONE
 #undef MZ_CHASE_STEP
-#if MZ_CHASE_LEAN
 #undef MZ_CHASE_RETARGET
-#endif
 #undef MZ_CHASE_RETIRE_TRIP
 #undef MZ_CHASE_RETIRE_CHASE_TRIP
 #undef MZ_CHASE_STORE_QUAD

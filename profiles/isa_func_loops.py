@@ -4,7 +4,7 @@ mz_chase_walk, mz_chase_emit -- from the compiler's own assembly of the default 
 instructions, selects, moves and vector-memory operations of each.  This is how the walk loops' refill is counted between GPU
 runs (profiles/r9).  Extra -D flags may be appended.
 
-    python profiles/isa_func_loops.py [function=mz_chase_walk] [min_instructions=100] [-DMZ_WALK_EDGE_BRANCH=0 ...]
+    python profiles/isa_func_loops.py [function=mz_chase_walk] [min_instructions=100] [-DMZ_CRC_CHAINS=1 ...]
 """
 import os
 import re

@@ -1,8 +1,8 @@
-"""Cases for two build knobs of K1: MZ_CHASE_LEAN (minizip-ng_amd/csrc/inflate_walk.inc: a chase takes its next target in front
-of a trip of four steps, not inside a step) and MZ_NEAR_PACKED (inflate_commit.inc: the near batches' rank searches on byte
-offsets, the short-period prologue from a packed constant).  Shared by tests/test_chase_lean_emul.py (the host emulation of every
-knob setting, and the sanitised stand-alone program) and tests/test_gpu_chase_lean.py (the device).  Every case is a stream zlib
-accepts; zlib's bytes are the expected ones (the tests assert it).
+"""Cases for two parts of K1: the chase of pass 2 (minizip-ng_amd/csrc/inflate_walk.inc: a chase takes its next target in front
+of a trip of four steps, not inside a step) and the set-up of the near batches (inflate_commit.inc: the rank searches on byte
+offsets, the short-period prologue from a packed constant).  Shared by tests/test_chase_lean_emul.py (the host emulation at the
+product's caps and at low ones, and the sanitised stand-alone program) and tests/test_gpu_chase_lean.py (the device).  Every case
+is a stream zlib accepts; zlib's bytes are the expected ones (the tests assert it).
 
     retarget()   where a chase runs through whole spans: level-1/6/9 text of 300 .. 2 000 bytes (spans at the 128-bit floor,
                  two to six steps each); 63-bit steps under 128-bit spans (a chase is in the next span but one after two steps,

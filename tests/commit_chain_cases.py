@@ -1,5 +1,6 @@
-"""The entries of tests/test_commit_chains_emul.py and tests/test_gpu_commit_chains.py: what the commit stage of K1
-(inflate_commit.inc) does differently under the build knobs MZ_CRC_CHAINS, MZ_NEAR_TAIL and MZ_EMIT_PREFETCH.
+"""The entries of tests/test_commit_chains_emul.py and tests/test_gpu_commit_chains.py, for three parts of the commit stage
+of K1 (inflate_commit.inc): the CRC fold of several super-tiles of a lane together (crc32_core.h, MZ_CRC_CHAINS), the tail of
+a near copy (inflate_core.h mz_copy32_seq) and the group of records an emit round loads (inflate_emit.inc).
 
   sizes()   entries whose output sizes stand on, one before and one behind every multiple of the 4 KiB super-tile up to a
             group of four, and at 32 / 64 KiB -- where the grouped CRC fold takes a group, leaves tiles pending, or has the

@@ -4,7 +4,7 @@ by the host emulation of the shipped kernel source built with -DMZ_STATS (counte
 bench corpus at level 6.  With profiles/isa_func_loops.py this recomputes a window's instruction budget without a GPU.  Not
 part of the product or the test suite.
 
-    python tests/study/k1_trips.py [extra -D flags, e.g. -DMZ_CHASE_LEAN=0]
+    python tests/study/k1_trips.py [extra -D flags, e.g. -DMZ_CHASE_SMAX=512u]
 """
 import ctypes as C
 import os

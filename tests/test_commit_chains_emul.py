@@ -1,11 +1,9 @@
-"""CPU tests of K1's commit stage under its three build knobs, on the 64-lane host emulation (tests/emul/emul.cpp built
-with -DMZHIP_HOST_EMUL): every combination of MZ_CRC_CHAINS in {1, 2, 4} (the CRC fold of C super-tiles of a lane together,
-crc32_core.h), MZ_NEAR_TAIL in {0, 1} (the tail of a near copy without a chain of small pairs, inflate_core.h
-mz_copy32_seq) and MZ_EMIT_PREFETCH in {0, 1} (the next emit round's records asked for when the cut is known,
-inflate_emit.inc).  The entries are tests/commit_chain_cases.py's; zlib judges bytes and CRC, and every build must give
-the same four result words for every entry."""
+"""CPU tests of K1's commit stage on the 64-lane host emulation (tests/emul/emul.cpp built with -DMZHIP_HOST_EMUL), once per
+setting of MZ_CRC_CHAINS in {1, 2, 4} (the CRC fold of C super-tiles of a lane together, crc32_core.h).  The entries are
+tests/commit_chain_cases.py's -- the group boundaries of the fold, and the tails of near copies (inflate_core.h mz_copy32_seq)
+behind the groups of records the emit rounds load (inflate_emit.inc); zlib judges bytes and CRC, and every build must give the
+same four result words for every entry."""
 import ctypes as C
-import itertools
 import os
 import subprocess
 import zlib
@@ -17,23 +15,22 @@ from tests import commit_chain_cases as cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _u8p = C.POINTER(C.c_uint8)
-KNOBS = list(itertools.product((1, 2, 4), (0, 1), (0, 1)))
+KNOBS = [1, 2, 4]
 
 
-def _build(knobs):
-    c, t, p = knobs
+def _build(c):
     out = os.path.join(ROOT, "tests", "emul", "_build")
     os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libemul_commit_c%d_t%d_p%d.so" % knobs)
-    subprocess.run(["g++", "-O1", "-Wno-unknown-pragmas", "-DMZHIP_HOST_EMUL", "-DMZ_CRC_CHAINS=%d" % c, "-DMZ_NEAR_TAIL=%d" % t,
-                    "-DMZ_EMIT_PREFETCH=%d" % p, "-I" + os.path.join(ROOT, "minizip-ng_amd", "csrc"), "-shared", "-fPIC",
+    so = os.path.join(out, "libemul_commit_c%d.so" % c)
+    subprocess.run(["g++", "-O1", "-Wno-unknown-pragmas", "-DMZHIP_HOST_EMUL", "-DMZ_CRC_CHAINS=%d" % c,
+                    "-I" + os.path.join(ROOT, "minizip-ng_amd", "csrc"), "-shared", "-fPIC",
                     os.path.join(ROOT, "tests", "emul", "emul.cpp"), "-o", so], check=True)
     return so
 
 
 @pytest.fixture(scope="module")
 def builds():
-    """{(chains, tail, prefetch): library}, compiled four at a time"""
+    """{chains: library}"""
     with ThreadPoolExecutor(4) as ex:
         sos = list(ex.map(_build, KNOBS))
     libs = {}

@@ -1,5 +1,5 @@
 """GPU test of two parts of K1 (minizip-ng_amd/csrc): the chase of pass 2 that takes its next target in front of a trip
-(inflate_walk.inc, MZ_CHASE_LEAN) and the near batches' set-up (inflate_commit.inc, MZ_NEAR_PACKED).  The cases of
+(inflate_walk.inc, MZ_CHASE_RETARGET) and the near batches' set-up (inflate_commit.inc, the rank searches).  The cases of
 tests/chase_lean_cases.py -- small entries whose chases run through whole spans, block ends and record caps inside chases, every
 short distance with every piece length at every staging phase -- repeated at other misalignments to a few thousand entries in
 ONE launch of mzhip_inflate_batch, and once more through mzhip_inflate_resume_batch (k_inflate_batch<true>, another compile of

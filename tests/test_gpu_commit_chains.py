@@ -1,5 +1,5 @@
 """GPU tests of K1's commit stage on the entries of tests/commit_chain_cases.py (the CPU twin on the host emulation, for
-every combination of the build knobs, is tests/test_commit_chains_emul.py): output sizes on, before and behind every group
+every number of CRC chains, is tests/test_commit_chains_emul.py): output sizes on, before and behind every group
 boundary of the CRC fold, and near-copy tails of every length at the distances next to 1 .. 8, 16 and 32 -- through
 mzhip_inflate_batch in one launch (byte by byte, and packed with every 16-byte misalignment of the output), and the sizes
 once more through the resumable path in two calls, so that the CRC of the second call starts behind history

@@ -33,7 +33,7 @@ def gpu():
 
 @pytest.fixture(scope="module")
 def emu():
-    """the host emulation of K1 alone, product knobs (tests/emul/walk_refill_main.cpp as a library)"""
+    """the host emulation of K1 alone, the product build (tests/emul/k1_walk_main.cpp as a library)"""
     from tests.test_walk_refill_emul import _build_variant
 
     return _build_variant("product", [])

@@ -1,51 +1,34 @@
-"""CPU tests of the refill of K1's two walks (minizip-ng_amd/csrc/inflate_walk.inc) in the 64-lane host emulation, once per
-setting of its two build knobs -- MZ_WALK_EDGE_BRANCH (the refill's loads: a group inside the input is one 16-byte load, the
-edge groups sit in a branch of their own) and MZ_WALK_TRIP_REFILL (one refill check per trip of four steps that may hand over
-both prefetched groups) -- and once more with record caps and spans so low that every window runs into them.  The cases are
-those of tests/walk_refill_cases.py; zlib is the judge of status, bytes, consumed input and CRC.
+"""CPU tests of the refill of K1's two walks (minizip-ng_amd/csrc/inflate_walk.inc) in the 64-lane host emulation: a group
+inside the input is one 16-byte load, the edge groups sit in a branch of their own, and one refill check per trip of four steps
+may hand over both prefetched groups.  Once at the product's span limit and record caps, and once more with record caps and
+spans so low that every window runs into them.  The cases are those of tests/walk_refill_cases.py; zlib is the judge of status,
+bytes, consumed input and CRC, and tests/golden/k1_walk_refill_baseline.json holds what the refill of one group per check
+behind selects, the code this one replaced, made of the cut streams.
 
-The last test compiles tests/emul/walk_refill_main.cpp, a program of its own, with -fsanitize=address,undefined and runs it as
+The last test compiles tests/emul/k1_walk_main.cpp, a program of its own, with -fsanitize=address,undefined and runs it as
 a child process: every case from a heap block that ends with the input's last aligned dword, at every misalignment.  (Not
 with the input's last byte: a decoder may read the aligned dwords that hold a byte of the input whole, include/mzhip.h, and
-mz_load_stream_dword does so for the last one in every build, the one before the knobs included.)"""
-import ctypes as C
+mz_load_stream_dword does so for the last one.)"""
+import hashlib
+import json
 import os
-import struct
-import subprocess
 import time
 import zlib
-from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
+from tests import k1_walk_emul
 from tests import walk_refill_cases as W
+from tests.k1_walk_emul import build_variant as _build_variant  # noqa: F401  (tests/test_gpu_walk_refill.py takes it from here)
 from tests.test_kernel_emul import _run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_u8p = C.POINTER(C.c_uint8)
-CAPS = ["-DMZ_CHASE_SMAX=512u", "-DMZ_REC_CAP1=16u", "-DMZ_REC_CAP2=8u"]
-BUILDS = [("e%dt%d%s" % (e, t, "_caps" if caps else ""), ["-DMZ_WALK_EDGE_BRANCH=%d" % e, "-DMZ_WALK_TRIP_REFILL=%d" % t] + (CAPS if caps else []))
-          for caps in (False, True) for e, t in ((0, 0), (1, 0), (0, 1), (1, 1))]
-
-
-def _build_variant(tag, flags):
-    out = os.path.join(ROOT, "tests", "emul", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libemul_walk_%s.so" % tag)
-    subprocess.run(["g++", "-O1", "-g", "-Wno-unknown-pragmas", "-DMZHIP_HOST_EMUL"] + flags +
-                   ["-I" + os.path.join(ROOT, "minizip-ng_amd", "csrc"), "-shared", "-fPIC",
-                    os.path.join(ROOT, "tests", "emul", "walk_refill_main.cpp"), "-o", so], check=True)   # (K1 alone: emul.cpp holds every core)
-    L = C.CDLL(so)
-    L.emul_inflate.argtypes = [_u8p, C.c_uint32, _u8p, C.c_uint32] + [C.POINTER(C.c_uint32)] * 3
-    return L
 
 
 @pytest.fixture(scope="module")
 def builds():
-    """{tag: library} of every knob setting at the product's span limit and record caps, and at 512 bits / 16 / 8 steps"""
-    with ThreadPoolExecutor(max_workers=4) as ex:
-        libs = list(ex.map(lambda b: _build_variant(*b), BUILDS))
-    return {tag: lib for (tag, _), lib in zip(BUILDS, libs)}
+    """{tag: library}: the product's span limit and record caps, and 512 bits / 16 / 8 steps"""
+    return k1_walk_emul.builds()
 
 
 def _check(tag, L, case, mis):
@@ -87,36 +70,25 @@ def test_every_cut(builds):
 
 
 def test_knobs_change_no_record(builds):
-    """What the walks hand on does not depend on the knobs: bytes, consumed input, CRC and status of every case are those of
-    the build with both knobs off (the code before them)."""
-    base = builds["e0t0"]
-    for case in W.everything()[:19] + W.everything()[19::37]:
-        name, z, _, _, _, cap = case
-        want = _run(base.emul_inflate, z, cap, mis=5)
-        for tag, L in builds.items():
-            if not tag.endswith("_caps"):
-                assert _run(L.emul_inflate, z, cap, mis=5) == want, (tag, name)
+    """What the walks hand on is what the refill before this one handed on: status, consumed input, bytes and CRC of every
+    case -- the cut streams included, where zlib pins the status alone -- are those recorded in
+    tests/golden/k1_walk_refill_baseline.json from the build its provenance field names."""
+    with open(os.path.join(ROOT, "tests", "golden", "k1_walk_refill_baseline.json")) as f:
+        base = json.load(f)["cases"]
+    cases = W.everything()[:19] + W.everything()[19::37]
+    assert set(base) == {c[0] for c in cases} and len(base) == len(cases)
+    for name, z, _, _, _, cap in cases:
+        st, iu, out, crc = _run(builds["product"].emul_inflate, z, cap, mis=5)
+        assert [st, iu, len(out), crc, hashlib.sha256(out).hexdigest()] == base[name], name
 
 
 def test_sanitised_program(tmp_path):
-    """tests/emul/walk_refill_main.cpp under AddressSanitizer and UBSan, the default (product) knobs: every case at every
-    misalignment from a heap block that ends with the input's last aligned dword; any read behind it ends the child with an
-    error report.  Its verdicts are zlib's."""
+    """tests/emul/k1_walk_main.cpp under AddressSanitizer and UBSan: every case at every misalignment of the input from a
+    heap block that ends with the input's last aligned dword; any read behind it ends the child with an error report.  Its
+    verdicts are zlib's."""
     t0 = time.time()
-    exe = str(tmp_path / "walk_refill_main")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                    "-Wno-unknown-pragmas", "-DMZHIP_HOST_EMUL", "-I" + os.path.join(ROOT, "minizip-ng_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "emul", "walk_refill_main.cpp"), "-o", exe], check=True)
     cases = W.everything()
-    blob = struct.pack("<I", len(cases)) + b"".join(struct.pack("<II", len(c[1]), c[5]) + c[1] for c in cases)
-    path = tmp_path / "cases.bin"
-    path.write_bytes(blob)
-    p = subprocess.run([exe, str(path)], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-3000:]
-    lines = p.stdout.split("\n")[:-1]
-    assert len(lines) == 16 * len(cases)
-    for line in lines:
-        c, mis, st, ol, iu, crc = (int(x) for x in line.split())
+    for c, mis, st, ol, iu, crc in k1_walk_emul.run_sanitised(tmp_path, "in", [(c[1], c[5]) for c in cases]):
         name, z, data, want, used, _ = cases[c]
         assert st == want, (name, mis, st, want)
         if want == 0:

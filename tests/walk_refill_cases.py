@@ -1,8 +1,8 @@
-"""Cases for the refill of K1's two walks (minizip-ng_amd/csrc/inflate_walk.inc, build knobs MZ_WALK_EDGE_BRANCH and
-MZ_WALK_TRIP_REFILL): what the refill decides depends on where the input ENDS relative to the aligned groups of four dwords
-the ring is topped up in, and on how fast a lane eats its ring.  Shared by tests/test_walk_refill_emul.py (the host emulation of
-every knob setting, and the sanitised stand-alone program) and tests/test_gpu_walk_refill.py (the device).  zlib's inflate is
-the judge of every case.
+"""Cases for the refill of K1's two walks (minizip-ng_amd/csrc/inflate_walk.inc: the edge groups in a branch of their own, one
+check per trip of four steps): what the refill decides depends on where the input ENDS relative to the aligned groups of four
+dwords the ring is topped up in, and on how fast a lane eats its ring.  Shared by tests/test_walk_refill_emul.py (the host
+emulation at the product's caps and at low ones, and the sanitised stand-alone program) and tests/test_gpu_walk_refill.py (the
+device).  zlib's inflate is the judge of every case.
 
     streams()   level-6 streams of 300 B .. 8 KiB of output whose lengths take every residue mod 16, plus one of 64 KiB (a
                 window with all 64 spans)
