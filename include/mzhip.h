@@ -434,6 +434,45 @@ MZHIP_API void mzhip_bzip2_encode_launch_geometry(uint32_t n, uint32_t max_in_le
 MZHIP_API int32_t mzhip_bzip2_encode_host(const uint8_t *in, uint32_t in_len, int32_t level, uint8_t *out, uint32_t out_cap,
                                           uint32_t *out_len, uint32_t *crc);
 
+/* Zstandard encode (ZIP method 93) ------------------------------------------------------- */
+
+/* Replaces, for n entries at once, mz_stream_zstd_write / _close (mz_strm_zstd.c -> libzstd ZSTD_compressStream2) +
+ * mz_crypt_crc32_update (mz_zip.c:2064).  Entry i's output is ONE frame of RFC 8878 without a dictionary id: Single_Segment
+ * with the smallest Frame_Content_Size field for entries of up to 8 MiB, a Window_Descriptor of exactly 8 MiB and a 4-byte
+ * content size beyond; one block per 64 KiB of input -- Compressed (Huffman, RLE or Raw literals; Predefined, RLE or
+ * FSE_Compressed sequence tables; never the Repeat or Treeless modes), RLE when its bytes are all equal, Raw when the
+ * compressed form is not smaller.  The LZ77 parse is the LZMA encoder's (one wave per 64 KiB block, matches up to 8 MiB
+ * back), then one wave per entry codes the tokens.  The bytes are valid Zstandard but not libzstd's: parity is
+ * "ZSTD_decompress returns the input".
+ * level: as mz_strm_zstd.c hands it to ZSTD_c_compressionLevel: 1 .. 22, -1 and 0 the default 3.  It chooses the parse:
+ * 1-2 one hash candidate per position and one far link, 3-6 four candidates and 4 links, 7-15 8 links, 16-22 16 links.
+ * Anything else returns MZ_PARAM_ERROR (-102) and launches nothing.  flags: bit 0 writes the XXH64 content checksum.
+ * n == 0 returns 0.  max_in_len = upper bound of d_in_len[]: it sizes the token scratch.
+ * Memory contract of the other encoders: the input is read at byte granularity, never outside d_in + d_in_off[i] .. +
+ * d_in_len[i], and is not changed; nothing is stored outside d_out + d_out_off[i] .. + d_out_cap[i], nor behind d_out_len[i]
+ * when the status is 0.  d_crc = CRC-32 of the INPUT.
+ * Status: 0; -200 the frame does not fit d_out_cap[i] (d_out_len[i] is 0 then; bytes inside the capacity may have been
+ * written).  d_out_cap[i] >= mzhip_zstd_encode_bound(d_in_len[i]) always suffices. */
+MZHIP_API int32_t mzhip_zstd_encode_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                          uint32_t max_in_len, void *d_out, const uint64_t *d_out_off,
+                                          const uint32_t *d_out_cap, uint32_t n, int32_t level, uint32_t flags,
+                                          uint32_t *d_out_len, uint32_t *d_crc, int32_t *d_status, void *stream);
+/* An output size that always suffices.  The frame header is 10 bytes at the most (4 of magic, the descriptor, the window
+ * byte or none, at most 4 of content size).  Every 64 KiB block begun (one for an empty input) costs a 3-byte header and
+ * never more than its own bytes: a Compressed block is written only when it is smaller than the data, an RLE block holds
+ * one byte, and the Raw fallback holds the data.  An optional checksum adds 4.  So
+ *   bound = 14 + in_len + 3 * max(1, ceil(in_len / 65536)). */
+MZHIP_API uint64_t mzhip_zstd_encode_bound(uint32_t in_len);
+/* What a mzhip_zstd_encode_batch launch would use: single-wave workgroups of the coding kernel (min(n, resident waves of the
+ * device)) and bytes of device scratch (tokens, the chain pass's links and tables when max_in_len exceeds one block, and per
+ * wave of the grid literals, sequence records and the staged block); (0, 0) for n == 0 or a level that is none. */
+MZHIP_API void mzhip_zstd_encode_launch_geometry(uint32_t n, uint32_t max_in_len, int32_t level, uint32_t *grid,
+                                                 uint64_t *scratch_bytes);
+/* one entry from a host buffer (H2D + kernels + D2H in one staging round trip, synchronous); *crc = CRC-32 of `in`.
+ * Returns the status: 0, -200 (the frame is longer than out_cap; *out_len is 0), -102 (level) */
+MZHIP_API int32_t mzhip_zstd_encode_host(const uint8_t *in, uint32_t in_len, int32_t level, uint32_t flags, uint8_t *out,
+                                         uint32_t out_cap, uint32_t *out_len, uint32_t *crc);
+
 /* Host-buffer conveniences (H2D + kernel + D2H, synchronous); these are what the
  * vtbl shims use for one-entry-at-a-time callers (raw DEFLATE: mzhip_inflate_host_a / mzhip_deflate_host_a above / below). */
 MZHIP_API int32_t mzhip_lzma_host(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_cap, int64_t max_out,

@@ -280,6 +280,45 @@ def bzip2_encode_host(data, level=6):
     return int(st), out.raw[: ol.value], int(crc.value)
 
 
+def zstd_encode_batch(d_in, in_off, in_len, d_out, out_off, out_cap, level=3, checksum=False):
+    """ZIP method 93, the write side: one Zstandard frame per entry through mzhip_zstd_encode_batch on torch's current stream
+    (asynchronous).  Tensors as for inflate_batch; level 1..22, -1 and 0 mean 3; checksum adds the XXH64 content checksum.
+    The token scratch is sized from the largest in_len (one copy of the lengths to the host).  Returns CUDA tensors
+    (out_len, crc, status); crc is the CRC-32 of the input."""
+    import torch
+
+    require_gpu()
+    n = in_off.numel()
+    dev = d_in.device
+    out_len, crc, status = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    for t, dt in ((in_off, torch.int64), (out_off, torch.int64), (in_len, torch.int32), (out_cap, torch.int32)):
+        assert t.dtype == dt and t.is_cuda and t.is_contiguous()
+    assert d_in.dtype == torch.uint8 and d_out.dtype == torch.uint8
+    max_in_len = int(in_len.max().item()) if n else 0
+    with torch.cuda.device(dev):
+        _check(lib().mzhip_zstd_encode_batch(d_in.data_ptr(), in_off.data_ptr(), in_len.data_ptr(), max_in_len, d_out.data_ptr(),
+                                             out_off.data_ptr(), out_cap.data_ptr(), n, level, 1 if checksum else 0,
+                                             out_len.data_ptr(), crc.data_ptr(), status.data_ptr(), _stream_handle()),
+               "mzhip_zstd_encode_batch")
+    return out_len, crc, status
+
+
+def zstd_encode_bound(in_len):
+    """mzhip_zstd_encode_bound: an output capacity that always suffices (host arithmetic, no device needed)"""
+    return int(lib().mzhip_zstd_encode_bound(in_len))
+
+
+def zstd_encode_host(data, level=3, checksum=False):
+    """One entry through the host-buffer convenience entry point -> (status, Zstandard frame, crc of the data)."""
+    require_gpu()
+    data = bytes(data)
+    cap = zstd_encode_bound(len(data))
+    out = C.create_string_buffer(cap)
+    ol, crc = C.c_uint32(0), C.c_uint32(0)
+    st = lib().mzhip_zstd_encode_host(data, len(data), level, 1 if checksum else 0, out, cap, C.byref(ol), C.byref(crc))
+    return int(st), out.raw[: ol.value], int(crc.value)
+
+
 def crc32_host(data, value=0):
     require_gpu()
     return int(lib().mzhip_crc32_host(value, bytes(data), len(data)))

@@ -468,6 +468,42 @@ int32_t mzhip_bzip2_encode_host(const uint8_t *in, uint32_t in_len, int32_t leve
     return m.status;
 }
 
+// One ZIP method-93 payload (a Zstandard frame) from a host buffer.
+int32_t mzhip_zstd_encode_host(const uint8_t *in, uint32_t in_len, int32_t level, uint32_t flags, uint8_t *out, uint32_t out_cap,
+                               uint32_t *out_len, uint32_t *crc) {
+    struct Meta {
+        uint64_t in_off, out_off;
+        uint32_t in_len, out_cap, out_len, crc;
+        int32_t status;
+    };
+    const uint64_t bound = mzhip_zstd_encode_bound(in_len);
+    if (level < -1 || level > 22 || bound > 0xFFFFFFFFull) return -102; /* MZ_PARAM_ERROR: no such level (or an entry whose bound needs 33 bits) */
+    HostCall<Meta> hc;
+    Meta &m = hc.m;
+    m.in_len = in_len;
+    m.out_cap = (uint32_t)bound;
+    m.in_off = hc.take(in_len, 64);
+    m.out_off = hc.take(m.out_cap, 64);
+    int32_t rc = hc.begin();
+    if (rc) return rc;
+    uint8_t *base = hc.at(0);
+    Meta *dm = hc.dm;
+    HIP_TRY(hc.put_meta());
+    if (in_len) HIP_TRY(mz_h2d(hc.at(m.in_off), in, in_len));
+    rc = mzhip_zstd_encode_batch(base, &dm->in_off, &dm->in_len, in_len, base, &dm->out_off, &dm->out_cap, 1, level, flags, &dm->out_len,
+                                 &dm->crc, &dm->status, MZ_HOST_STREAM);
+    if (rc) return rc;
+    HIP_TRY(hc.wait_fetch_meta());
+    if (m.status == 0 && m.out_len > out_cap) {
+        m.status = MZHIP_STATUS_OUT_FULL;
+        m.out_len = 0;
+    }
+    if (m.status == 0 && m.out_len) HIP_TRY(mz_d2h(out, hc.at(m.out_off), m.out_len));
+    give(out_len, m.out_len);
+    give(crc, m.crc);
+    return m.status;
+}
+
 // ... then the index over all blocks and the stream footer (host arithmetic only: a few dozen bytes)
 int32_t mzhip_xz_encode_finish_host(const uint64_t *unpadded_size, const uint64_t *uncompressed_size, uint32_t nblocks, uint8_t *out,
                                     uint32_t out_cap, uint32_t *out_len) {

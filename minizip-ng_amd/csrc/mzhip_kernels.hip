@@ -42,6 +42,7 @@
 #include "crypt_core.h"
 #include "bzip2_core.h"
 #include "bzip2_enc_core.h"
+#include "zstd_enc_core.h"
 #include "zstd_core.h"
 
 #ifndef MZ_WAVES_PER_WG
@@ -877,6 +878,40 @@ __global__ __launch_bounds__(64) void k_lzma_rc_encode_batch(LzmaEncArgs a) {
         mz_lzma_enc_result r;
         mz_lzma_rc_encode(in, MZ_UNIFORM(a.in_len[e]), a.tok + (size_t)e * a.maxb * MZ_DEF_BLOCK, a.ntok + (size_t)e * a.maxb,
                           a.mode ? MZ_UNIFORM((uint32_t)a.mode[e]) : 0u, out, MZ_UNIFORM(a.out_cap[e]), &lds, crc_tab, a.tabs, &r);
+        a.out_len[e] = r.out_len;
+        a.crc[e] = r.crc;
+        a.status[e] = r.status;
+    }
+}
+
+struct ZstdEncArgs {
+    LzmaEncArgs a;           // the parse's arguments (mode null): entries, token blocks, counters, CRC tables
+    uint8_t *scratch;        // MZ_ZSE_SCRATCH_BYTES per wave of the grid: literals, sequence records, the staged block body
+    uint32_t flags;          // bit 0: write the XXH64 content checksum
+};
+
+// zstd encode (ZIP method 93), behind K6's parse: one wave per workgroup and per entry codes the entry's token blocks as one
+// frame (zstd_enc_core.h), 14.6 KiB of LDS (bit window, Huffman's queues, the three FSE coding tables and their
+// descriptions), persistent waves over the parse's third counter.
+__global__ __launch_bounds__(64) void k_zstd_encode_batch(ZstdEncArgs z) {
+    __shared__ __attribute__((aligned(16))) mz_zse_lds lds;
+    __shared__ uint32_t crc_tab[256];
+    const LzmaEncArgs &a = z.a;
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) crc_tab[i] = a.tabs->byte_tab[i];
+    __syncthreads();
+    MZ_LANE_DECL
+    uint8_t *const scratch = z.scratch + (size_t)blockIdx.x * MZ_ZSE_SCRATCH_BYTES;
+    for (;;) {
+        uint32_t e;
+        MZ_WAVE_FETCH_ADD(e, a.counter + 1);
+        if (e >= a.n) break;
+        const uint64_t io = a.in_off[e], oo = a.out_off[e];
+        const uint8_t *in = a.in + MZ_UNIFORM64(io);
+        uint8_t *out = a.out + MZ_UNIFORM64(oo);
+        mz_zse_result r;
+        mz_zstd_enc_entry(in, MZ_UNIFORM(a.in_len[e]), a.tok + (size_t)e * a.maxb * MZ_DEF_BLOCK, a.ntok + (size_t)e * a.maxb, out,
+                          MZ_UNIFORM(a.out_cap[e]), z.flags, &lds, crc_tab, a.tabs, scratch, &r);
+        // wave-uniform results: stored by all lanes (same address, same value), see MZ_WAVE_FETCH_ADD
         a.out_len[e] = r.out_len;
         a.crc[e] = r.crc;
         a.status[e] = r.status;

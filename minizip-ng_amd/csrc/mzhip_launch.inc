@@ -722,6 +722,82 @@ int32_t mzhip_lzma_encode_batch_preset(const void *d_in, const uint64_t *d_in_of
     return launched("k_lzma_rc_encode_batch", hipGetLastError(), sc);
 }
 
+/* zstd encode: K6's parse (token scratch as for LZMA: 4 bytes per input position of the largest entry for every entry, as
+ * much again and the chain pass's tables when an entry has more than one block), then one wave per entry.  That wave owns
+ * MZ_ZSE_SCRATCH_BYTES = 263 168 of the scratch: the block's literals, its sequence records and the staged body.  8
+ * single-wave workgroups per CU, two per SIMD (15.6 KiB of LDS each would allow 10; 253 VGPRs allow 8): the FSE walk is a chain of dependent LDS
+ * reads, so a wave mostly waits.  A full grid on a 256-CU device holds 514 MiB of it.  grid = min(n, resident). */
+#define MZ_ZSE_WAVES_PER_CU 8u
+
+static uint32_t zstd_enc_grid(const DeviceCtx *c, uint32_t n) { return resident_grid(n, (uint32_t)c->cu_count * MZ_ZSE_WAVES_PER_CU); }
+
+/* the bytes of one launch's scratch: tokens, links and chain tables, token counts, three counters, the coder's part */
+static size_t zstd_enc_scratch(uint32_t n, uint32_t maxb, uint32_t grid, uint32_t *chain_waves_out, size_t *tok_words_out,
+                               size_t *link_words_out, size_t *coder_off_out) {
+    const size_t items = (size_t)n * maxb;
+    const size_t tok_words = items * MZ_DEF_BLOCK;
+    const uint32_t chain_waves = maxb > 1u ? resident_grid(n, MZ_LZE_CHAIN_WAVES) : 0u;
+    const size_t link_words = chain_waves ? tok_words + ((size_t)chain_waves << MZ_LZE_FAR_HBITS) : 0u;
+    const size_t coder_off = (((tok_words + link_words + items + 3u) * sizeof(uint32_t)) + 255u) & ~(size_t)255u;
+    if (chain_waves_out) *chain_waves_out = chain_waves;
+    if (tok_words_out) *tok_words_out = tok_words;
+    if (link_words_out) *link_words_out = link_words;
+    if (coder_off_out) *coder_off_out = coder_off;
+    return coder_off + (size_t)grid * MZ_ZSE_SCRATCH_BYTES;
+}
+
+uint64_t mzhip_zstd_encode_bound(uint32_t in_len) { return MZ_ZSE_BOUND(in_len); }
+
+void mzhip_zstd_encode_launch_geometry(uint32_t n, uint32_t max_in_len, int32_t level, uint32_t *grid, uint64_t *scratch_bytes) {
+    DeviceCtx *c = nullptr;
+    uint32_t g = 0;
+    if (n && MZ_ZSE_LEVEL_OK(level) && ctx_for_current(&c) == 0) g = zstd_enc_grid(c, n);
+    if (grid) *grid = g;
+    if (scratch_bytes)
+        *scratch_bytes = g ? zstd_enc_scratch(n, max_in_len ? (max_in_len + MZ_DEF_BLOCK - 1) / MZ_DEF_BLOCK : 1u, g, nullptr, nullptr, nullptr, nullptr) : 0u;
+}
+
+int32_t mzhip_zstd_encode_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, uint32_t max_in_len,
+                                void *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap, uint32_t n, int32_t level,
+                                uint32_t flags, uint32_t *d_out_len, uint32_t *d_crc, int32_t *d_status, void *stream) {
+    if (!MZ_ZSE_LEVEL_OK(level)) {
+        snprintf(g_err, sizeof(g_err), "mzhip_zstd_encode_batch: level %d is not -1 .. 22", (int)level);
+        return -102; /* MZ_PARAM_ERROR */
+    }
+    if (n == 0) return 0;
+    Launch L;
+    int32_t rc = L.begin(stream, false); /* (three work counters of its own, in the scratch) */
+    if (rc) return rc;
+    DeviceCtx *c = L.c;
+    hipStream_t s = L.s;
+    ZstdEncArgs z;
+    LzmaEncArgs &a = z.a;
+    set_fields(a, c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, nullptr, d_crc, d_status);
+    a.mode = nullptr;
+    a.maxb = max_in_len ? (max_in_len + MZ_DEF_BLOCK - 1) / MZ_DEF_BLOCK : 1u;
+    set_lz_class(c, a, MZ_ZSE_PRESET(level));
+    const uint32_t grid = zstd_enc_grid(c, n);
+    uint32_t chain_waves = 0;
+    size_t tok_words = 0, link_words = 0, coder_off = 0;
+    const size_t bytes = zstd_enc_scratch(n, a.maxb, grid, &chain_waves, &tok_words, &link_words, &coder_off);
+    const size_t items = (size_t)n * a.maxb;
+    ScratchLease sc;
+    rc = sc.get(&c->scratch, bytes, s);
+    if (rc) return rc;
+    a.tok = (uint32_t *)sc.p;
+    a.links = chain_waves ? a.tok + tok_words : nullptr;
+    a.chain_head = chain_waves ? a.links + tok_words : nullptr;
+    a.skip_blocks = 0;
+    a.ntok = a.tok + tok_words + link_words;
+    a.counter = a.ntok + items; /* three work counters behind the token counts */
+    z.scratch = (uint8_t *)sc.p + coder_off;
+    z.flags = flags;
+    HIP_TRY(hipMemsetAsync(a.counter, 0, 3 * sizeof(uint32_t), s));
+    launch_lz_parse(c, s, a, chain_waves);
+    hipLaunchKernelGGL(k_zstd_encode_batch, dim3(grid), dim3(64), 0, s, z);
+    return launched("k_zstd_encode_batch", hipGetLastError(), sc);
+}
+
 } // extern "C"
 
 // ---- one window of one large entry, a wave per DEFLATE block (the orchestration: inflate_parallel.inc)
