@@ -267,6 +267,30 @@ MZHIP_API int32_t mzhip_zstd_host(const uint8_t *in, uint32_t in_len, uint8_t *o
  * and bytes of device scratch (a block's literals, per wave of the grid). */
 MZHIP_API void mzhip_zstd_launch_geometry(uint32_t n, uint32_t *grid, uint64_t *scratch_bytes);
 
+/* ONE large method-93 entry, device-resident, decoded by a wave per Zstandard block (mzhip_zstd_batch gives an entry one
+ * wave: a few MiB/s on an entry of many MiB).  A block's end stands in its header, so one wave walks the headers (scan),
+ * a wave per Compressed block builds its tables and runs the FSE machine without executing anything (count: the bytes it
+ * produces, and its repeat offsets as a function of the incoming ones), the host names for every block the earlier block
+ * whose Huffman tree or sequence table it repeats and composes positions and repeat offsets, a wave per block writes
+ * literals and, per match byte, the index of its source (emit), pointer jumping resolves that source map window after
+ * window (window_bytes of output each, 0 = the default of 128 MiB; the map costs 4 bytes per output byte), one wave per
+ * frame folds XXH64 (csrc/zstd_par_core.h, csrc/zstd_parallel.inc).  d_in / d_out are device pointers, the results host
+ * pointers (any may be NULL); *out_len, *in_used, *crc and *status are exactly what mzhip_zstd_batch gives for the same
+ * entry: on any problem in any pass, and for an entry of more than 32 768 blocks, the call decodes the whole entry with
+ * that kernel and says so in stats->fallback.  An entry of any size is taken.  Synchronous on `stream`. */
+typedef struct mzhip_zstd_large_stats {
+    uint32_t size;      /* = sizeof: copy min(size, known) as the *_args structs do */
+    uint32_t windows;
+    uint32_t blocks;    /* blocks decoded by a wave of their own */
+    uint32_t borrowed;  /* of those, blocks whose tree or a table came from an earlier block */
+    uint32_t rounds;    /* pointer-jump rounds */
+    uint32_t fallback;  /* 0 no; 1 a problem was met; 2 block cap; 3 scratch */
+} mzhip_zstd_large_stats;
+
+MZHIP_API int32_t mzhip_zstd_large(const void *d_in, uint32_t in_len, void *d_out, uint32_t out_cap, uint32_t window_bytes,
+                                   uint32_t *out_len, uint32_t *in_used, uint32_t *crc, int32_t *status,
+                                   mzhip_zstd_large_stats *stats, void *stream);
+
 /* SHA-1 / SHA-224 / SHA-256 / SHA-384 / SHA-512 of n buffers ----------------------------- */
 
 /* What the reader's hash verification computes per entry on the CPU: mz_crypt_sha_begin/_update/_end over the

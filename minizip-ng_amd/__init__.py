@@ -232,6 +232,31 @@ def zstd_batch(d_in, in_off, in_len, d_out, out_off, out_cap):
     return out_len, in_used, crc, status
 
 
+class ZstdLargeStats(C.Structure):
+    """include/mzhip.h mzhip_zstd_large_stats"""
+    _fields_ = [("size", C.c_uint32), ("windows", C.c_uint32), ("blocks", C.c_uint32), ("borrowed", C.c_uint32),
+                ("rounds", C.c_uint32), ("fallback", C.c_uint32)]
+
+
+def zstd_large(d_in, d_out, window_bytes=0):
+    """ZIP method 93, ONE large entry: the Zstandard frames in the uint8 CUDA tensor d_in decoded into d_out (its size is the
+    capacity) by a wave per block through mzhip_zstd_large on torch's current stream (synchronous).  window_bytes = 0 is the
+    default window.  Returns (status, out_len, in_used, crc, stats): the first four exactly what zstd_batch gives for the
+    entry, stats a dict of windows, blocks, borrowed, rounds and fallback (0: decoded by waves of their own)."""
+    import torch
+
+    require_gpu()
+    assert d_in.dtype == torch.uint8 and d_out.dtype == torch.uint8 and d_in.is_cuda and d_out.is_cuda
+    assert d_in.is_contiguous() and d_out.is_contiguous() and d_in.numel() < 2**32 and d_out.numel() < 2**32
+    ol, iu, crc, st = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_int32(0)
+    stats = ZstdLargeStats(size=C.sizeof(ZstdLargeStats))
+    with torch.cuda.device(d_in.device):
+        _check(lib().mzhip_zstd_large(d_in.data_ptr(), d_in.numel(), d_out.data_ptr(), d_out.numel(), window_bytes, C.byref(ol),
+                                      C.byref(iu), C.byref(crc), C.byref(st), C.byref(stats), _stream_handle()), "mzhip_zstd_large")
+    return (int(st.value), int(ol.value), int(iu.value), int(crc.value),
+            dict((k, int(getattr(stats, k))) for k in ("windows", "blocks", "borrowed", "rounds", "fallback")))
+
+
 def zstd_host(data, out_cap):
     """One entry's Zstandard frames through the host-buffer convenience entry point -> (status, in_used, out bytes, crc)."""
     require_gpu()

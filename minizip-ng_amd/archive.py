@@ -154,6 +154,7 @@ def gather_results(results, world, group=None):
 
 
 LARGE_ENTRY = 4 << 20   # compressed bytes from which a DEFLATE entry is decoded by a wave per block (as mzhip_prime_* does)
+LARGE_ZSTD_ENTRY = 4 << 20   # ... and a Zstandard entry by a wave per block (mzhip_zstd_large)
 
 
 class DeviceArchive:
@@ -290,8 +291,22 @@ class DeviceArchive:
                         raise _mz.MzHipError("mzhip_inflate_large failed: %d %s" % (rc, L.mzhip_last_error().decode()))
                     crc[e], out_len[e] = ck.value, ol.value
                     status[e] = MZ_CRC_ERROR if (st1.value == 0 and iu.value == p_len[e] and not skip_crc[e] and ck.value != np.uint32(t[e, COL_CRC])) else st1.value
+                # ... and Zstandard entries of LARGE_ZSTD_ENTRY compressed bytes and more by a wave per Zstandard block
+                # (mzhip_zstd_large, csrc/zstd_parallel.inc): every field is what the batch launch gives for the entry
+                large_z = np.nonzero((meth == 93) & from_here & (p_len >= LARGE_ZSTD_ENTRY))[0]
+                if len(large_z) and ((p_len[large_z] >= 2**31) | (usize[large_z] >= 2**31)).any():
+                    raise _mz.MzHipError("entries >= 2 GiB are outside the batch path")
+                for e in large_z:
+                    ol, iu, ck, st1 = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_int32()
+                    rc = L.mzhip_zstd_large(d_src.data_ptr() + int(p_off[e]), int(p_len[e]), d_out.data_ptr() + int(out_off[e]),
+                                            int(usize[e]), 0, C.byref(ol), C.byref(iu), C.byref(ck), C.byref(st1), None, stream)
+                    if rc != 0:
+                        raise _mz.MzHipError("mzhip_zstd_large failed: %d %s" % (rc, L.mzhip_last_error().decode()))
+                    crc[e], out_len[e] = ck.value, ol.value
+                    status[e] = MZ_CRC_ERROR if (st1.value == 0 and iu.value == p_len[e] and not skip_crc[e] and ck.value != np.uint32(t[e, COL_CRC])) else st1.value
+                routed = ((meth == 8) & (p_len >= LARGE_ENTRY)) | ((meth == 93) & (p_len >= LARGE_ZSTD_ENTRY))
                 for method in (8, 12, 93, 14, 95, 0):
-                    sel = np.nonzero((meth == method) & from_here & ~((meth == 8) & (p_len >= LARGE_ENTRY)))[0]
+                    sel = np.nonzero((meth == method) & from_here & ~routed)[0]
                     if len(sel) == 0:
                         continue
                     k = len(sel)

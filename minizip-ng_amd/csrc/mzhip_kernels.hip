@@ -44,6 +44,7 @@
 #include "bzip2_enc_core.h"
 #include "zstd_enc_core.h"
 #include "zstd_core.h"
+#include "zstd_par_core.h"
 
 #ifndef MZ_WAVES_PER_WG
 #define MZ_WAVES_PER_WG 4
@@ -328,6 +329,57 @@ __global__ __launch_bounds__(64) void k_zstd_batch(ZstdArgs a) {
         a.in_used[e] = r.in_used;
         a.crc[e] = r.crc;
         a.status[e] = r.status;
+    }
+}
+
+// ---- one large Zstandard entry, a wave per block (zstd_par_core.h; the host logic: zstd_parallel.inc)
+struct ZstdScanArgs {
+    const uint8_t *in;
+    uint32_t in_len, blk_cap;
+    uint32_t *recs, *frms, *hdr;
+};
+// the headers of the whole entry on one wave
+__global__ __launch_bounds__(64) void k_zstd_scan(ZstdScanArgs a) {
+    __shared__ __attribute__((aligned(16))) mz_zs_lds lds;
+    mz_zsp_scan(a.in, a.in_len, &lds, a.recs, a.frms, a.blk_cap, a.hdr);
+}
+
+struct ZstdBlocksArgs {
+    const uint8_t *in;
+    uint32_t in_len;
+    uint8_t *out;
+    uint32_t *ptr; // the source map, biased: ptr[i] belongs to out[i]
+    const uint32_t *jobs;
+    uint32_t n, mode;
+    uint32_t *res;
+    uint32_t *counter;
+    uint8_t *scratch; // MZ_ZS_SCRATCH_BYTES per wave of the grid, as in k_zstd_batch
+};
+// a wave per block (persistent waves over a counter, single-wave workgroups as in k_zstd_batch): mode 1 counts, mode 2
+// writes literals and the source map
+__global__ __launch_bounds__(64) void k_zstd_blocks(ZstdBlocksArgs a) {
+    __shared__ __attribute__((aligned(16))) mz_zs_lds lds;
+    MZ_LANE_DECL
+    uint8_t *const scratch = a.scratch + (size_t)blockIdx.x * MZ_ZS_SCRATCH_BYTES;
+    for (;;) {
+        uint32_t e;
+        MZ_WAVE_FETCH_ADD(e, a.counter);
+        if (e >= a.n) break;
+        mz_zsp_block(a.in, a.in_len, a.jobs + (size_t)e * MZ_ZSP_JOB_WORDS, a.mode, a.out, a.ptr, &lds, scratch, a.res + (size_t)e * MZ_ZSP_RES_WORDS);
+    }
+}
+
+struct ZstdXxhArgs {
+    const uint8_t *out;
+    const uint32_t *spans; // per frame: its first output byte, its length
+    uint32_t n;
+    uint32_t *vals;
+};
+// the content checksum of a frame, a wave per frame: XXH64 is one serial chain per frame
+__global__ __launch_bounds__(64) void k_zstd_frame_xxh(ZstdXxhArgs a) {
+    for (uint32_t e = blockIdx.x; e < a.n; e += gridDim.x) {
+        const uint32_t v = mz_zsp_xxh64(a.out + MZ_UNIFORM(a.spans[2u * e]), MZ_UNIFORM(a.spans[2u * e + 1u]));
+        a.vals[e] = v;
     }
 }
 

@@ -1093,6 +1093,230 @@ int32_t mzhip_inflate_large(const void *d_in, uint32_t in_len, void *d_out, uint
     return 0;
 }
 
+} // extern "C"
+
+// ---- one large Zstandard entry, a wave per block (the orchestration: zstd_parallel.inc)
+#include "zstd_parallel.inc"
+namespace {
+struct DevZstdLargeBackend {
+    DeviceCtx *c;
+    hipStream_t s;
+    const uint8_t *d_in;
+    uint32_t in_len;
+    uint8_t *d_out;
+    uint32_t *d_map; // the source map of one window
+    uint32_t map_n;
+    uint32_t *d_recs, *d_frms, *d_hdr, *d_jobs, *d_res, *d_flag;
+    uint32_t cap; // blocks the arrays hold
+    double t_scan = 0, t_pass[3] = {0, 0, 0}, t_resolve = 0, t_xxh = 0; // MZHIP_PAR_TRACE=1: seconds per step (each ends in a blocking copy)
+    int32_t scan(uint32_t blk_cap, std::vector<uint32_t> &recs, std::vector<uint32_t> &frms, uint32_t *hdr) {
+        const double t0 = DevParBackend::now();
+        if (blk_cap > cap) return -104;
+        ZstdScanArgs a;
+        a.in = d_in;
+        a.in_len = in_len;
+        a.blk_cap = blk_cap;
+        a.recs = d_recs;
+        a.frms = d_frms;
+        a.hdr = d_hdr;
+        hipLaunchKernelGGL(k_zstd_scan, dim3(1), dim3(64), 0, s, a);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(mz_d2h_on(s, hdr, d_hdr, MZ_ZSP_HDR_WORDS * 4));
+        const uint32_t nb = hdr[MZ_ZSP_H_NBLK], nf = hdr[MZ_ZSP_H_NFRM];
+        if (nb > blk_cap || nf > blk_cap) return -104;
+        recs.resize((size_t)nb * MZ_ZSP_REC_WORDS);
+        frms.resize((size_t)nf * MZ_ZSP_FRM_WORDS);
+        if (nb && hdr[MZ_ZSP_H_STOP] == 0) HIP_TRY(mz_d2h_on(s, recs.data(), d_recs, recs.size() * 4));
+        if (nf && hdr[MZ_ZSP_H_STOP] == 0) HIP_TRY(mz_d2h_on(s, frms.data(), d_frms, frms.size() * 4));
+        t_scan += DevParBackend::now() - t0;
+        return 0;
+    }
+    int32_t blocks(uint32_t mode, const uint32_t *jobs, uint32_t n, uint32_t bias, uint32_t *res) {
+        const double t0 = DevParBackend::now();
+        if (n == 0 || n > cap) return -104;
+        if (mode == 2u && jobs[(size_t)(n - 1u) * MZ_ZSP_JOB_WORDS + MZ_ZSP_J_END] - bias > map_n) return -104;
+        HIP_TRY(mz_h2d_on(s, d_jobs, jobs, (size_t)n * MZ_ZSP_JOB_WORDS * 4));
+        ZstdBlocksArgs a;
+        a.in = d_in;
+        a.in_len = in_len;
+        a.out = d_out;
+        a.ptr = (uint32_t *)((uintptr_t)d_map - 4u * (uintptr_t)bias);
+        a.jobs = d_jobs;
+        a.n = n;
+        a.mode = mode;
+        a.res = d_res;
+        CounterLease head;
+        int32_t rc = head.get(&c->counters, s);
+        if (rc) return rc;
+        a.counter = head.p;
+        const uint32_t grid = zstd_grid(c, n);
+        ScratchLease sc;
+        rc = sc.get(&c->scratch, (size_t)grid * MZ_ZS_SCRATCH_BYTES, s);
+        if (rc) return rc;
+        a.scratch = (uint8_t *)sc.p;
+        hipLaunchKernelGGL(k_zstd_blocks, dim3(grid), dim3(64), 0, s, a);
+        rc = launched("k_zstd_blocks", hipGetLastError(), sc);
+        if (rc) return rc;
+        HIP_TRY(mz_d2h_on(s, res, d_res, (size_t)n * MZ_ZSP_RES_WORDS * 4));
+        t_pass[mode & 3u] += DevParBackend::now() - t0;
+        return 0;
+    }
+    // the DEFLATE path's kernels over a biased map: roots are literals and everything in front of the window
+    int32_t resolve(uint32_t w0, uint32_t w1, uint32_t *rounds) {
+        const double t0 = DevParBackend::now();
+        if (w1 - w0 > map_n) return -104;
+        ParJumpArgs a;
+        a.out = d_out;
+        a.ptr = (uint32_t *)((uintptr_t)d_map - 4u * (uintptr_t)w0);
+        a.hist = w0;
+        a.total = w1;
+        a.changed = d_flag;
+        const uint64_t want = ((uint64_t)(w1 - w0) + 255u) / 256u;
+        const uint32_t grid = resident_grid(want ? want : 1u, (uint64_t)c->cu_count * 32u);
+        for (uint32_t r = 0; r < 40u; r++) {
+            HIP_TRY(hipMemsetAsync(d_flag, 0, 4, s));
+            hipLaunchKernelGGL(k_ptr_jump, dim3(grid), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_ptr_jump, dim3(grid), dim3(256), 0, s, a);
+            HIP_TRY(hipGetLastError());
+            uint32_t changed = 0;
+            HIP_TRY(mz_d2h_on(s, &changed, d_flag, 4));
+            *rounds += 2;
+            if (!changed) break;
+        }
+        hipLaunchKernelGGL(k_ptr_gather, dim3(grid), dim3(256), 0, s, a);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+        t_resolve += DevParBackend::now() - t0;
+        return 0;
+    }
+    int32_t xxh(const uint32_t *spans, uint32_t n, uint32_t *vals) { /* (the jobs and results of the passes are done with) */
+        const double t0 = DevParBackend::now();
+        if (n > cap) return -104;
+        HIP_TRY(mz_h2d_on(s, d_jobs, spans, (size_t)n * 8));
+        ZstdXxhArgs a;
+        a.out = d_out;
+        a.spans = d_jobs;
+        a.n = n;
+        a.vals = d_res;
+        hipLaunchKernelGGL(k_zstd_frame_xxh, dim3(resident_grid(n, (uint64_t)c->cu_count * 8u)), dim3(64), 0, s, a);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(mz_d2h_on(s, vals, d_res, (size_t)n * 4));
+        t_xxh += DevParBackend::now() - t0;
+        return 0;
+    }
+};
+} // namespace
+
+extern "C" {
+
+// One large Zstandard entry, device-resident, by a wave per block (include/mzhip.h).  Synchronous: the host composes what
+// crosses blocks; everything is queued on `stream` and waited for there.
+int32_t mzhip_zstd_large(const void *d_in, uint32_t in_len, void *d_out, uint32_t out_cap, uint32_t window_bytes, uint32_t *out_len,
+                         uint32_t *in_used, uint32_t *crc, int32_t *status, mzhip_zstd_large_stats *stats, void *stream) {
+    DeviceCtx *c = nullptr;
+    int32_t rc = ctx_for_current(&c);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t window = window_bytes ? window_bytes : MZ_LARGE_WINDOW;
+    DevZstdLargeBackend be;
+    be.c = c;
+    be.s = s;
+    be.d_in = (const uint8_t *)d_in;
+    be.in_len = in_len;
+    be.d_out = (uint8_t *)d_out;
+    be.cap = in_len / 3u + 1u < MZ_ZSP_BLOCK_CAP ? in_len / 3u + 1u : MZ_ZSP_BLOCK_CAP;
+    be.map_n = window > MZ_ZS_BLOCK_MAX ? window : MZ_ZS_BLOCK_MAX;
+    if (be.map_n > out_cap) be.map_n = out_cap;
+    const auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t ck_max = (size_t)out_cap / 65536u + 3;
+    const size_t o_recs = pad((size_t)be.map_n * 4 + 64), o_frms = o_recs + pad((size_t)be.cap * MZ_ZSP_REC_WORDS * 4);
+    const size_t o_hdr = o_frms + pad(((size_t)be.cap + 1u) * MZ_ZSP_FRM_WORDS * 4), o_jobs = o_hdr + 256;
+    const size_t o_res = o_jobs + pad((size_t)be.cap * MZ_ZSP_JOB_WORDS * 4), o_meta = o_res + pad((size_t)be.cap * MZ_ZSP_RES_WORDS * 4);
+    const size_t o_ck = o_meta + 256, total = o_ck + ck_max * 16;
+    ScratchLease sc;
+    rc = sc.get(&c->scratch, total, s);
+    MzZsLarge r;
+    uint32_t k = 0, ol = 0, iu = 0;
+    int32_t st = 0;
+    double t_crc = 0, t_one = 0;
+    if (rc) { /* no room for the map and the arrays: the one-wave reader needs neither */
+        r.fallback = 3u;
+        (void)hipGetLastError();
+    } else {
+        uint8_t *base = (uint8_t *)sc.p;
+        be.d_map = (uint32_t *)base;
+        be.d_recs = (uint32_t *)(base + o_recs);
+        be.d_frms = (uint32_t *)(base + o_frms);
+        be.d_hdr = (uint32_t *)(base + o_hdr);
+        be.d_flag = be.d_hdr + 16;
+        be.d_jobs = (uint32_t *)(base + o_jobs);
+        be.d_res = (uint32_t *)(base + o_res);
+        rc = mz_zstd_large_entry(be, in_len, out_cap, window, &r);
+        if (!rc && !r.fallback) {
+            const double t0 = DevParBackend::now();
+            ol = r.out_len;
+            iu = in_len;
+            if (crc && ol) rc = window_checksums(be.d_out, 0, 0, ol, &k, nullptr, base + o_ck, ck_max, s);
+            t_crc = DevParBackend::now() - t0;
+        }
+        const int32_t rr = sc.release();
+        if (!rc) rc = rr;
+        if (rc) return rc;
+    }
+    if (r.fallback) { /* the whole entry through the one-wave kernel: its statuses, lengths and bytes */
+        const double t0 = DevParBackend::now();
+        struct Meta {
+            uint64_t in_off, out_off;
+            uint32_t in_len, out_cap, out_len, in_used, crc;
+            int32_t status;
+        } m;
+        memset(&m, 0, sizeof(m));
+        m.in_len = in_len;
+        m.out_cap = out_cap;
+        ScratchLease ms;
+        rc = ms.get(&c->scratch, 256, s);
+        if (rc) return rc;
+        Meta *dm = (Meta *)ms.p;
+        hipError_t e = mz_h2d_on(s, dm, &m, sizeof(m));
+        if (e == hipSuccess) {
+            rc = mzhip_zstd_batch(d_in, &dm->in_off, &dm->in_len, d_out, &dm->out_off, &dm->out_cap, 1, &dm->out_len, &dm->in_used, &dm->crc,
+                                  &dm->status, s);
+            if (!rc) e = mz_d2h_on(s, &m, dm, sizeof(m));
+        }
+        const int32_t rr = ms.release();
+        if (e != hipSuccess) return fail("mzhip_zstd_large: the one-wave reader", e);
+        if (!rc) rc = rr;
+        if (rc) return rc;
+        ol = m.out_len;
+        iu = m.in_used;
+        k = m.crc;
+        st = m.status;
+        t_one = DevParBackend::now() - t0;
+    }
+    if (par_trace())
+        fprintf(stderr,
+                "mzhip zstd large: %u B in, %u B out, status %d, fallback %u; %u windows, %u blocks (%u borrowed), %u rounds; ms: scan %.3f count %.3f "
+                "emit %.3f resolve %.3f xxh64 %.3f crc %.3f one-wave %.3f\n",
+                in_len, ol, st, r.fallback, r.windows, r.blocks, r.borrowed, r.rounds, be.t_scan * 1e3, be.t_pass[1] * 1e3, be.t_pass[2] * 1e3,
+                be.t_resolve * 1e3, be.t_xxh * 1e3, t_crc * 1e3, t_one * 1e3);
+    if (out_len) *out_len = ol;
+    if (in_used) *in_used = iu;
+    if (crc) *crc = k;
+    if (status) *status = st;
+    if (stats) {
+        mzhip_zstd_large_stats v;
+        const uint32_t n = stats->size < (uint32_t)sizeof(v) ? stats->size : (uint32_t)sizeof(v);
+        v.size = n;
+        v.windows = r.windows;
+        v.blocks = r.blocks;
+        v.borrowed = r.borrowed;
+        v.rounds = r.rounds;
+        v.fallback = r.fallback;
+        memcpy(stats, &v, n);
+    }
+    return 0;
+}
+
 // (tests) the header search alone over host bytes placed `misalign` bytes behind a 16-byte boundary on the device: which = 0 the
 // product's kernel, 1 the one-offset-per-lane kernel it replaced.  out[0 .. min(*n, cap)) = the candidates, in no order.
 int32_t mzhip_find_blocks_host(const uint8_t *in, uint32_t in_len, uint32_t b0, uint32_t b1, int32_t which, uint32_t misalign, uint32_t *out,
