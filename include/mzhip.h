@@ -20,6 +20,13 @@
  *     independent entries per launch, inputs and outputs resident in HBM.
  *     Plain pointers and sizes only; `stream` is a hipStream_t passed as
  *     void* (NULL = the default stream).  All d_* pointers are device pointers.
+ *     Every launch is ordered on `stream`: behind whatever the caller queued there before the call (the copy that brings
+ *     the input, the kernel that writes the offsets) and in front of whatever it queues after it; no call waits for the
+ *     stream, except the ones documented as synchronous (mzhip_inflate_large, mzhip_zstd_large, the *_host calls).
+ *     hipStreamPerThread may be passed from any number of threads at once.  Offsets are full 64-bit values: an entry may
+ *     lie anywhere in an allocation of any size, across offset 2^32 or a 4 GiB-aligned address, and an out_cap may be any
+ *     32-bit value the room behind it holds (tests/test_gpu_launch_contract.py holds every batch entry point to this
+ *     paragraph).  Stream capture (hipGraph) is not promised: the launchers create events and may allocate.
  *
  * Status words are numerically the reference's (mz.h:21-26): 0 OK,
  * -3 MZ_DATA_ERROR, -5 MZ_BUF_ERROR (input ended early), plus

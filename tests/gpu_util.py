@@ -17,7 +17,8 @@ def guard_pattern(nbytes, seed):
     return np.random.RandomState(seed).randint(1, 256, size=nbytes, dtype=np.uint8)
 
 
-def make_batch(payloads, out_caps, align=16, device="cuda:0", guard=0, fill=None, packed=False, odd=False):
+def make_batch(payloads, out_caps, align=16, device="cuda:0", guard=0, fill=None, packed=False, odd=False, upload_payloads=True,
+               into=None):
     """payloads: list[bytes] of raw-deflate streams; out_caps: list[int].
     -> dict of CUDA tensors laid out the way the C ABI wants them.
 
@@ -25,7 +26,13 @@ def make_batch(payloads, out_caps, align=16, device="cuda:0", guard=0, fill=None
     fill: seed of the byte pattern (guard_pattern) written over the WHOLE of d_out and over the gaps of d_in before the
     launch; None = zeros, today's layout.  packed: no alignment and no red zone between entries (out_off[i + 1] ==
     out_off[i] + out_cap[i], the layout of bench.py); the red zones stay in front and behind.  odd: every out_off odd
-    (red-zone layout only).  The dict keeps host copies of the pattern (h_fill) and of d_in (h_in)."""
+    (red-zone layout only).  The dict keeps host copies of the pattern (h_fill) and of d_in (h_in).
+    upload_payloads=False: d_in on the device holds the gaps' bytes alone; the caller uploads the payload bytes itself (h_in
+    is what d_in must hold at the launch, payload_blob() the same layout around other payloads of the same lengths).
+    into=(big_in, in_base, big_out, out_base): the same layout placed at byte in_base of the uint8 device tensor big_in and at
+    out_base of big_out (which must have the room): d_in / d_out are views of those places, in_off / out_off on the device
+    count from the big tensors' first bytes -- p_in / p_out, what a call is handed -- and h_in_off / h_out_off stay local, so
+    check_guards judges the placed layout like any other."""
     import torch
 
     n = len(payloads)
@@ -54,12 +61,40 @@ def make_batch(payloads, out_caps, align=16, device="cuda:0", guard=0, fill=None
     pos += guard - between if n else 0
     h_fill = np.zeros(max(pos, 16), dtype=np.uint8) if fill is None else guard_pattern(max(pos, 16), fill)
     dev = torch.device(device)
+    up = blob
+    if not upload_payloads:
+        up = blob.copy()
+        gaps = np.zeros(up.size, dtype=np.uint8) if fill is None else guard_pattern(up.size, fill + 1)
+        for i, p in enumerate(payloads):
+            up[in_off[i]:in_off[i] + len(p)] = gaps[in_off[i]:in_off[i] + len(p)]
+    in_base = out_base = 0
+    if into is None:
+        d_in, d_out = torch.from_numpy(up).to(dev), torch.from_numpy(h_fill.copy()).to(dev)
+        root_in, root_out = d_in, d_out
+    else:
+        root_in, in_base, root_out, out_base = into
+        assert 0 <= in_base and in_base + up.size <= root_in.numel() and 0 <= out_base and out_base + h_fill.size <= root_out.numel()
+        d_in, d_out = root_in[in_base:in_base + up.size], root_out[out_base:out_base + h_fill.size]
+        d_in.copy_(torch.from_numpy(up))
+        d_out.copy_(torch.from_numpy(h_fill))
     return dict(
-        d_in=torch.from_numpy(blob).to(dev), in_off=torch.from_numpy(in_off).to(dev),
+        d_in=d_in, in_off=torch.from_numpy(in_off + in_base).to(dev),
         in_len=torch.from_numpy(in_len.astype(np.int32)).to(dev),
-        d_out=torch.from_numpy(h_fill.copy()).to(dev), out_off=torch.from_numpy(out_off).to(dev),
+        d_out=d_out, out_off=torch.from_numpy(out_off + out_base).to(dev),
         out_cap=torch.from_numpy(out_cap.astype(np.int32)).to(dev), h_out_off=out_off, n=n,
-        h_out_cap=out_cap, h_in_off=in_off, h_in_len=in_len, h_in=blob.copy(), h_fill=h_fill, guard=guard, packed=packed)
+        h_out_cap=out_cap, h_in_off=in_off, h_in_len=in_len, h_in=blob.copy(), h_fill=h_fill, guard=guard, packed=packed,
+        p_in=root_in.data_ptr(), p_out=root_out.data_ptr(), in_base=in_base, out_base=out_base)
+
+
+def payload_blob(batch, payloads):
+    """what d_in of `batch` holds with other payloads of the same lengths at the same places"""
+    blob = batch["h_in"].copy()
+    for i, p in enumerate(payloads):
+        assert len(p) == int(batch["h_in_len"][i])
+        if p:
+            o = int(batch["h_in_off"][i])
+            blob[o:o + len(p)] = np.frombuffer(p, dtype=np.uint8)
+    return blob
 
 
 def guarded_results(n, names, words=None, device="cuda:0"):
