@@ -4,6 +4,12 @@
 // launch kernels themselves).  The rest of the host runtime is built apart from this translation unit (mzhip_host.cpp,
 // mzhip_crc_host.cpp, mzhip_prime.cpp); mzhip_runtime.h is the seam.
 //
+// Argument structs: a batch kernel takes one struct by value.  What every batch call describes alike -- the two blobs, the
+// per-entry arrays, the work counter, the CRC tables -- is EntryTable, declared once below; InflateArgs, LzmaArgs,
+// WaveScratchArgs (bzip2 and zstd decode), Bzip2EncArgs, DeflateArgs, LzmaEncArgs, PkcryptArgs and WzaesArgs (each both
+// directions) derive from it and hold only their own fields.  The persistent loop and the result stores are written out in
+// every kernel on purpose: a shared helper around them changed K1's code (DESIGN section 7 has what that once cost).
+//
 // Launch shape of K1 (MI355X: 256 CUs x 4 SIMDs, 160 KiB LDS/CU, 8 XCDs):
 //   - one wavefront per ZIP entry, 4 wavefronts per workgroup, 9.98 KiB of LDS per wave: 3.8 KiB of Huffman tables, 4.75 KiB
 //     of per-lane stream rings while the lanes walk (the chase window, inflate_walk.inc), 1.2 KiB of pool -- and while the
@@ -24,6 +30,7 @@
 #include <shared_mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 #include <dlfcn.h>
@@ -78,7 +85,21 @@ extern "C" __attribute__((visibility("default"))) int mzhip_prof_read(unsigned l
 #define MZ_MIN_WAVES_PER_SIMD 4 /* register budget: 128 VGPRs -> 4 waves per SIMD, 16 per CU (matches the LDS budget: 4 workgroups) */
 #endif
 
-struct InflateArgs {
+// The entry table: how every batch entry point of the C ABI (include/mzhip.h) describes its work -- one input blob, one
+// output blob and, per entry, where it lies in each and where its results go -- plus what the launcher adds.  This is the one
+// place these fields are declared; the argument struct of every batch kernel derives from it and adds only what is its own.
+//   - in, in_off, in_len, out, out_off, n, out_len, status: set by every launcher, read by every kernel.
+//   - out_cap: null for the crypt kernels (their ABI has no capacities: an entry's output size follows from its input size).
+//   - in_used: null for every encoder and the crypt kernels (they take the whole input or fail); the decoders store it.
+//   - crc: null for the crypt kernels; everyone else stores the CRC-32 of the plain bytes.
+//   - counter: the work-queue head of persistent waves -- the launch's leased head (Launch::head, zeroed by the lease), or
+//     three words of the launch's own scratch for K6's parse (zeroed by the launcher).  Null where a kernel takes a lane or a
+//     workgroup per entry from its grid index (ZipCrypto).
+//   - tabs: the device's CRC tables; set by set_fields for everyone, unused by the WinZip-AES kernels.
+// A launcher value-initialises its struct (`Args a{};`), so a field nobody assigns is null or zero, never garbage.
+// The order is InflateArgs's from before there was a base, on purpose: with it K1's argument block, and so its code, is
+// byte for byte what it was (the static_assert behind InflateArgs).
+struct EntryTable {
     const uint8_t *in;
     const uint64_t *in_off;
     const uint32_t *in_len;
@@ -92,10 +113,20 @@ struct InflateArgs {
     int32_t *status;
     uint32_t *counter;
     const mzhip_crc_tables *tabs;
+};
+// a kernel argument struct is copied into the launch's argument block byte by byte
+#define MZ_ARGS_CHECK(A) static_assert(std::is_trivially_copyable<A>::value && std::is_base_of<EntryTable, A>::value, #A " : EntryTable, plain bytes")
+
+struct InflateArgs : EntryTable {
     uint8_t *rec; // MZ_REC_BYTES of step-record scratch per wave of the grid (chase window), or null
     const mz_inflate_state *resume; // per entry: take the stream up at this state (window-by-window decode), or null
     mz_inflate_state *stop;         // per entry: where it can be taken up again, or null
 };
+MZ_ARGS_CHECK(InflateArgs);
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof" /* (fields in base and derived: not standard-layout, the offset is well defined here all the same) */
+static_assert(offsetof(InflateArgs, rec) == sizeof(EntryTable), "K1's own fields start where the table ends, as before it was a base");
+#pragma clang diagnostic pop
 
 // Two instantiations: RESUMABLE = false is the batch as mzhip_inflate_batch launches it (no entry is taken up or left in the
 // middle: a.resume and a.stop are null, and the compiler drops the resume bookkeeping -- which block the cursor is in, where the
@@ -194,27 +225,15 @@ __global__ __launch_bounds__(MZ_WAVES_PER_WG * 64) void k_adler32_batch(CrcArgs 
     }
 }
 
-struct LzmaArgs {
-    const uint8_t *in;
-    const uint64_t *in_off;
-    const uint32_t *in_len;
-    uint8_t *out;
-    const uint64_t *out_off;
-    const uint32_t *out_cap;
+struct LzmaArgs : EntryTable {
     const int64_t *max_out; // may be null: no TOTAL_OUT_MAX clamp
-    uint32_t n;
-    uint32_t *out_len;
-    uint32_t *in_used;
-    uint32_t *crc;
-    int32_t *status;
-    uint32_t *counter;
-    const mzhip_crc_tables *tabs;
     const uint64_t *tab64; // CRC-64 byte table (.xz kernel only)
     uint16_t *xprobs;      // MZ_LZMA_XPROBS u16 per resident wave: upper half of the literal model when lc + lp = 4
     uint16_t *sprobs;      // slot kernel: MZ_LZMA_SPROBS u16 per resident wave, the whole literal model
     uint32_t *retry_list;  // slot kernel: entries given back (MZHIP_RETRY) are appended here, ...
     uint32_t *retry_n;     // ... counted here; the full-model kernel then decodes exactly those (list != null: n = *retry_n)
 };
+MZ_ARGS_CHECK(LzmaArgs);
 
 // K3: one wave per workgroup, the wave's whole probability model (15.6 KiB) in LDS -> 10 waves per CU.
 #ifdef MZ_LZMA_WAVES /* measurement builds (profiles/r3/scripts/ab_k3.sh): waves per SIMD the register allocation is held to */
@@ -246,26 +265,17 @@ __global__ __launch_bounds__(64) void k_lzma_batch(LzmaArgs a) {
     }
 }
 
-struct Bzip2Args {
-    const uint8_t *in;
-    const uint64_t *in_off;
-    const uint32_t *in_len;
-    uint8_t *out;
-    const uint64_t *out_off;
-    const uint32_t *out_cap;
-    uint32_t n;
-    uint32_t *out_len;
-    uint32_t *in_used;
-    uint32_t *crc;
-    int32_t *status;
-    uint32_t *counter;
-    const mzhip_crc_tables *tabs;
-    uint8_t *scratch; // MZ_BZ_SCRATCH_BYTES per wave of the grid: the inverse BWT's links, the block's bytes, the selectors
+// The decoders that take a wave per entry in single-wave workgroups and a fixed slice of HBM scratch per wave of the grid:
+//   k_bzip2_batch  MZ_BZ_SCRATCH_BYTES: the inverse BWT's links, the block's bytes, the selectors
+//   k_zstd_batch   MZ_ZS_SCRATCH_BYTES: the literals of the block being decoded
+struct WaveScratchArgs : EntryTable {
+    uint8_t *scratch;
 };
+MZ_ARGS_CHECK(WaveScratchArgs);
 
 // bzip2 (ZIP method 12): one wave per workgroup and per entry (bzip2_core.h), 10.4 KiB of LDS (tables, MTF list, byte
 // counts, input window, the two CRC tables), persistent waves over a counter as in k_lzma_batch.
-__global__ __launch_bounds__(64) void k_bzip2_batch(Bzip2Args a) {
+__global__ __launch_bounds__(64) void k_bzip2_batch(WaveScratchArgs a) {
     __shared__ __attribute__((aligned(16))) mz_bz_lds lds;
     __shared__ uint32_t crc_tab[256];
     for (int i = threadIdx.x; i < 256; i += blockDim.x) crc_tab[i] = a.tabs->byte_tab[i];
@@ -289,26 +299,9 @@ __global__ __launch_bounds__(64) void k_bzip2_batch(Bzip2Args a) {
     }
 }
 
-struct ZstdArgs {
-    const uint8_t *in;
-    const uint64_t *in_off;
-    const uint32_t *in_len;
-    uint8_t *out;
-    const uint64_t *out_off;
-    const uint32_t *out_cap;
-    uint32_t n;
-    uint32_t *out_len;
-    uint32_t *in_used;
-    uint32_t *crc;
-    int32_t *status;
-    uint32_t *counter;
-    const mzhip_crc_tables *tabs;
-    uint8_t *scratch; // MZ_ZS_SCRATCH_BYTES per wave of the grid: the literals of the block being decoded
-};
-
 // Zstandard (ZIP method 93): one wave per workgroup and per entry (zstd_core.h), 11.1 KiB of LDS (the Huffman and the three
 // FSE decode tables, the input window, the CRC byte table), persistent waves over a counter as in k_bzip2_batch.
-__global__ __launch_bounds__(64) void k_zstd_batch(ZstdArgs a) {
+__global__ __launch_bounds__(64) void k_zstd_batch(WaveScratchArgs a) {
     __shared__ __attribute__((aligned(16))) mz_zs_lds lds;
     __shared__ uint32_t crc_tab[256];
     for (int i = threadIdx.x; i < 256; i += blockDim.x) crc_tab[i] = a.tabs->byte_tab[i];
@@ -383,24 +376,12 @@ __global__ __launch_bounds__(64) void k_zstd_frame_xxh(ZstdXxhArgs a) {
     }
 }
 
-struct Bzip2EncArgs {
-    const uint8_t *in;
-    const uint64_t *in_off;
-    const uint32_t *in_len;
-    uint8_t *out;
-    const uint64_t *out_off;
-    const uint32_t *out_cap;
-    uint32_t n;
-    uint32_t *out_len;
-    uint32_t *crc;
-    int32_t *status;
-    uint32_t *counter;
-    const mzhip_crc_tables *tabs;
-    uint8_t *scratch;       // scratch_stride bytes per wave of the grid: rotation orders, ranks / symbols, the block, the selectors
+struct Bzip2EncArgs : WaveScratchArgs { // scratch: scratch_stride bytes per wave of the grid: rotation orders, ranks / symbols, the block, the selectors
     uint64_t scratch_stride; // MZ_BZE_SCRATCH_BYTES(cap_syms)
     uint32_t cap_syms;      // MZ_BZE_CAP_SYMS(max_in_len, level)
     uint32_t level;         // the block-size digit, 1 .. 9
 };
+MZ_ARGS_CHECK(Bzip2EncArgs);
 
 // bzip2 encode (ZIP method 12): one wave per workgroup and per entry (bzip2_enc_core.h), 27.8 KiB of LDS (bit window, the
 // tables' frequencies, lengths and codes, Huffman's queues, MTF list, the two CRC tables), persistent waves over a counter.
@@ -585,19 +566,14 @@ __global__ __launch_bounds__(256, 4) void k_sha_batch(ShaArgs a) {
 }
 
 // K8: the crypt streams of password-protected entries, read side (crypt_core.h).
-struct PkcryptArgs {
-    const uint8_t *in;
-    const uint64_t *in_off;
-    const uint32_t *in_len;
-    uint8_t *out;
-    const uint64_t *out_off;
-    uint32_t n;
+// Both directions; the random bytes of the write side (ZipCrypto header, AES salt) are the caller's.
+struct PkcryptArgs : EntryTable {
     uint32_t k0, k1, k2;    // the three keys after the password (host: mz_pk_init_keys_host)
-    const uint32_t *verify; // per entry: check bytes and whether byte 10 counts, see mzhip_pkcrypt_batch
-    uint32_t *out_len;
-    int32_t *status;
-    const mzhip_crc_tables *tabs;
+    const uint32_t *verify; // per entry, read side: check bytes and whether byte 10 counts, see mzhip_pkcrypt_batch;
+                            // write side: bits 8-15 -> plain header byte 10, bits 0-7 -> byte 11
+    const uint8_t *header;  // write side, per entry: the 10 free header bytes; null on the way in
 };
+MZ_ARGS_CHECK(PkcryptArgs);
 
 // ZipCrypto: the key recurrence is serial in an entry's bytes, so ONE LANE decrypts one entry (64 per wave).
 __global__ __launch_bounds__(256) void k_pkcrypt_batch(PkcryptArgs a) {
@@ -612,21 +588,14 @@ __global__ __launch_bounds__(256) void k_pkcrypt_batch(PkcryptArgs a) {
     a.out_len[e] = out_len;
 }
 
-struct WzaesArgs {
-    const uint8_t *in;
-    const uint64_t *in_off;
-    const uint32_t *in_len;
+struct WzaesArgs : EntryTable {
     const uint8_t *strength;
-    uint8_t *out;
-    const uint64_t *out_off;
-    uint32_t n;
+    const uint8_t *salt; // write side, per entry: a 16-byte record, 4 s + 4 bytes of it used; null on the way in
     uint32_t password_len;
     uint8_t password[MZ_WZAES_PW_MAX];
-    uint32_t *out_len;
-    int32_t *status;
-    uint32_t *counter;
     mz_wzaes_entry_keys *keys; // n records of scratch
 };
+MZ_ARGS_CHECK(WzaesArgs);
 
 // Key derivation: one lane per (entry, PBKDF2 block) -- four lane slots per entry, of which 2, 3 or 4 work -- then, behind a
 // workgroup barrier (an entry's slots sit in one workgroup), the slot-0 lane checks the verifier, expands the AES key and
@@ -685,24 +654,9 @@ __global__ __launch_bounds__(256, 4) void k_wzaes_auth(WzaesArgs a) {
     if (st != 0) a.status[e] = st;
 }
 
-// K8, write side: the same streams in the encrypting direction.  The random bytes (ZipCrypto header, AES salt) are the caller's.
-struct PkcryptEncArgs {
-    const uint8_t *in;
-    const uint64_t *in_off;
-    const uint32_t *in_len;
-    uint8_t *out;
-    const uint64_t *out_off;
-    uint32_t n;
-    uint32_t k0, k1, k2;    // the three keys after the password (host: mz_pk_init_keys_host)
-    const uint32_t *verify; // per entry: bits 8-15 -> plain header byte 10, bits 0-7 -> byte 11
-    const uint8_t *header;  // per entry: the 10 free header bytes
-    uint32_t *out_len;
-    int32_t *status;
-    const mzhip_crc_tables *tabs;
-};
-
+// K8, write side: the same streams in the encrypting direction.
 // ZipCrypto: ONE LANE encrypts one entry, as k_pkcrypt_batch decrypts it.
-__global__ __launch_bounds__(256) void k_pkcrypt_enc_batch(PkcryptEncArgs a) {
+__global__ __launch_bounds__(256) void k_pkcrypt_enc_batch(PkcryptArgs a) {
     __shared__ uint32_t crc_tab[256];
     for (int i = threadIdx.x; i < 256; i += blockDim.x) crc_tab[i] = a.tabs->byte_tab[i];
     __syncthreads();
@@ -714,26 +668,9 @@ __global__ __launch_bounds__(256) void k_pkcrypt_enc_batch(PkcryptEncArgs a) {
     a.out_len[e] = out_len;
 }
 
-struct WzaesEncArgs {
-    const uint8_t *in;
-    const uint64_t *in_off;
-    const uint32_t *in_len;
-    const uint8_t *strength;
-    const uint8_t *salt; // per entry a 16-byte record, 4 s + 4 bytes of it used
-    uint8_t *out;
-    const uint64_t *out_off;
-    uint32_t n;
-    uint32_t password_len;
-    uint8_t password[MZ_WZAES_PW_MAX];
-    uint32_t *out_len;
-    int32_t *status;
-    uint32_t *counter;
-    mz_wzaes_entry_keys *keys; // n records of scratch
-};
-
 // Key derivation as k_wzaes_keys: four lane slots per entry, a workgroup barrier, then the slot-0 lane -- which here has
 // nothing to compare: it writes salt and verifier to the front of the entry's output.  No lane leaves before the barrier.
-__global__ __launch_bounds__(256) void k_wzaes_enc_keys(WzaesEncArgs a) {
+__global__ __launch_bounds__(256) void k_wzaes_enc_keys(WzaesArgs a) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, e = t >> 2, b = t & 3u;
     const bool live = e < a.n;
     const uint8_t *salt = nullptr;
@@ -756,7 +693,7 @@ __global__ __launch_bounds__(256) void k_wzaes_enc_keys(WzaesEncArgs a) {
 
 // AES-CTR as k_wzaes_ctr, plaintext in: one wave per entry on the persistent grid, the ciphertext goes behind the salt and the
 // verifier (4 s + 6 bytes off the input's alignment).  Entries whose key step refused them are skipped.
-__global__ __launch_bounds__(MZ_WAVES_PER_WG * 64) void k_wzaes_enc_ctr(WzaesEncArgs a) {
+__global__ __launch_bounds__(MZ_WAVES_PER_WG * 64) void k_wzaes_enc_ctr(WzaesArgs a) {
     __shared__ mz_aes_tables tab;
     for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) mz_aes_table_entry(&tab, i);
     __syncthreads();
@@ -778,7 +715,7 @@ __global__ __launch_bounds__(MZ_WAVES_PER_WG * 64) void k_wzaes_enc_ctr(WzaesEnc
 
 // Authentication: one lane per entry.  Unlike k_wzaes_auth it reads what the CTR kernel WROTE, so it must be queued behind
 // that kernel on the same stream; it is the only writer of the entry's last 10 bytes.
-__global__ __launch_bounds__(256, 4) void k_wzaes_enc_auth(WzaesEncArgs a) {
+__global__ __launch_bounds__(256, 4) void k_wzaes_enc_auth(WzaesArgs a) {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= a.n) return;
     const mz_wzaes_entry_keys *ek = a.keys + e;
@@ -786,26 +723,15 @@ __global__ __launch_bounds__(256, 4) void k_wzaes_enc_auth(WzaesEncArgs a) {
     mz_wzaes_enc_auth(a.out + a.out_off[e], a.in_len[e], a.strength[e], ek);
 }
 
-struct DeflateArgs {
-    const uint8_t *in;
-    const uint64_t *in_off;
-    const uint32_t *in_len;
-    uint8_t *out;
-    const uint64_t *out_off;
-    const uint32_t *out_cap;
+struct DeflateArgs : EntryTable {
     const uint8_t *final_flag; // may be null: every piece is a complete stream
     const uint32_t *warm;      // may be null (0): bytes in front of a piece, in the same blob, that it may match into (mz_deflate_piece)
-    uint32_t n;
-    uint32_t *out_len;
-    uint32_t *crc;
-    int32_t *status;
-    uint32_t *counter;
-    const mzhip_crc_tables *tabs;
     uint32_t *tok; // token scratch: MZ_DEF_BLOCK words per resident wave
     uint32_t ways; // hash-bucket depth of the match finder: 1 (levels 1-3) or MZ_DEF_WAYS_BEST (levels 4-9, -1)
     uint32_t parse; // 1: cost parse over every block (levels 7-9), 0: the lazy rule per step (levels 4-6 and -1; always with ways == 1)
     uint32_t max_dist; // largest match distance: window - 262
 };
+MZ_ARGS_CHECK(DeflateArgs);
 
 #define MZ_DEF_LDS_STRIDE ((sizeof(mz_deflate_lds) + 15) & ~(size_t)15)
 
@@ -846,29 +772,18 @@ __global__ __launch_bounds__(MZ_WAVES_PER_WG * 64) void k_deflate_batch(DeflateA
 // levels 7-9: the same piece loop with the cost parse compiled in (160 VGPRs; this class runs one workgroup per CU anyway)
 __global__ __launch_bounds__(MZ_WAVES_PER_WG * 64) void k_deflate_cost_batch(DeflateArgs a) { deflate_batch_body<1u>(a); }
 
-struct LzmaEncArgs {
-    const uint8_t *in;
-    const uint64_t *in_off;
-    const uint32_t *in_len;
-    uint8_t *out;
-    const uint64_t *out_off;
-    const uint32_t *out_cap;
+struct LzmaEncArgs : EntryTable { // counter: three heads (block parse, coder, chain pass) in the launch's own scratch
     const uint8_t *mode; // may be null (all 0): 0 = ZIP method-14 payload, 1 = raw LZMA2 chunk payload
-    uint32_t n;
     uint32_t maxb; // 64 KiB blocks reserved per entry in tok / ntok
     uint32_t ways; // hash candidates per position in the LZ77 parse (1 or MZ_DEF_WAYS_BEST), by preset
     uint32_t *tok;
     uint32_t *ntok;
-    uint32_t *out_len;
-    uint32_t *crc;
-    int32_t *status;
-    uint32_t *counter;
-    const mzhip_crc_tables *tabs;
-    uint32_t *links;       // chain pass: 4 bytes per input position, laid out like tok; null = no stream of more than one block
+    uint32_t *links;      // chain pass: 4 bytes per input position, laid out like tok; null = no stream of more than one block
     uint32_t *chain_head;  // chain pass: 1 << MZ_LZE_FAR_HBITS words per resident wave of k_lz_chain_batch
     uint32_t skip_blocks;  // blocks in front of every entry that are history only (a stream written in segments): not parsed
     uint32_t far_depth;    // links of the chain the block parse follows per position (MZ_LZE_DEPTH_FOR_PRESET)
 };
+MZ_ARGS_CHECK(LzmaEncArgs);
 
 // LZMA encode, pass 0: the chain pass, one wave per method-14 stream of more than one block (lzma_enc_core.h mz_lz_chain)
 __global__ __launch_bounds__(64) void k_lz_chain_batch(LzmaEncArgs a) {

@@ -108,17 +108,9 @@ int32_t launched(const char *what, hipError_t le, ScratchLease &sc) {
 // Persistent waves: the workgroups the work needs, at most the ones that are resident at once (fill the chip once).
 uint32_t resident_grid(uint64_t need, uint64_t resident) { return (uint32_t)(need < resident ? need : resident); }
 
-// The fields the argument structs of the batch kernels name alike; a.f = v where the struct has a field f, nothing otherwise.
-#define MZ_OPTIONAL_FIELD(f)                                                                               \
-    template <class A, class V> auto set_##f(A &a, V v, int) -> decltype((void)(a.f = v)) { a.f = v; } \
-    template <class A, class V> void set_##f(A &, V, long) {}
-MZ_OPTIONAL_FIELD(out_cap)
-MZ_OPTIONAL_FIELD(in_used)
-MZ_OPTIONAL_FIELD(crc)
-MZ_OPTIONAL_FIELD(tabs)
-MZ_OPTIONAL_FIELD(tab64)
-template <class A>
-void set_fields(A &a, const DeviceCtx *c, const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
+// The entry table of a batch call (EntryTable, mzhip_kernels.hip) from the call's arguments; a call whose ABI lacks one of
+// the arrays passes nullptr for it, in so many words.  `counter` is the launcher's to set.
+void set_fields(EntryTable &a, const DeviceCtx *c, const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
                 const uint64_t *d_out_off, const uint32_t *d_out_cap, uint32_t n, uint32_t *d_out_len, uint32_t *d_in_used,
                 uint32_t *d_crc, int32_t *d_status) {
     a.in = (const uint8_t *)d_in;
@@ -126,13 +118,13 @@ void set_fields(A &a, const DeviceCtx *c, const void *d_in, const uint64_t *d_in
     a.in_len = d_in_len;
     a.out = (uint8_t *)d_out;
     a.out_off = d_out_off;
-    set_out_cap(a, d_out_cap, 0);
+    a.out_cap = d_out_cap;
     a.n = n;
     a.out_len = d_out_len;
-    set_in_used(a, d_in_used, 0);
-    set_crc(a, d_crc, 0);
+    a.in_used = d_in_used;
+    a.crc = d_crc;
     a.status = d_status;
-    set_tabs(a, c->d_tabs, 0);
+    a.tabs = c->d_tabs;
 }
 
 template <class A>
@@ -150,16 +142,16 @@ uint32_t grid_for(const DeviceCtx *c, uint32_t n) {
     return resident_grid(wgs_needed ? wgs_needed : 1u, (uint32_t)(c->cu_count * c->inflate_wgs_per_cu));
 }
 
-// ZipCrypto, both directions: a lane per entry; `a` arrives with the fields only one direction has
-template <class A>
-int32_t pkcrypt_batch(A &a, void (*kernel)(A), const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
-                             const uint64_t *d_out_off, uint32_t n, const uint8_t *password, uint32_t password_len,
-                             const uint32_t *d_verify, uint32_t *d_out_len, int32_t *d_status, void *stream) {
+// ZipCrypto, both directions: a lane per entry; d_header is the write side's (null on the way in)
+int32_t pkcrypt_batch(void (*kernel)(PkcryptArgs), const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
+                      const uint64_t *d_out_off, uint32_t n, const uint8_t *password, uint32_t password_len,
+                      const uint32_t *d_verify, const uint8_t *d_header, uint32_t *d_out_len, int32_t *d_status, void *stream) {
     if (!password) return MZ_CRYPT_PARAM_ERROR;
     if (n == 0) return 0;
     Launch L;
     const int32_t rc = L.begin(stream, false);
     if (rc) return rc;
+    PkcryptArgs a{};
     set_fields(a, L.c, d_in, d_in_off, d_in_len, d_out, d_out_off, nullptr, n, d_out_len, nullptr, nullptr, d_status);
     uint32_t keys[3];
     mz_pk_init_keys_host(password, password_len, keys);
@@ -167,27 +159,29 @@ int32_t pkcrypt_batch(A &a, void (*kernel)(A), const void *d_in, const uint64_t 
     a.k1 = keys[1];
     a.k2 = keys[2];
     a.verify = d_verify;
+    a.header = d_header;
     hipLaunchKernelGGL(kernel, dim3((n + 255) / 256), dim3(256), 0, L.s, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 // WinZip-AES, both directions: the entries' keys (four lanes an entry), CTR over the payloads (the work queue), the HMAC
-// a lane per entry -- on the way in behind the CTR kernel: it authenticates the ciphertext that kernel wrote
-template <class A>
-int32_t wzaes_batch(A &a, const Kernel<A> (&k)[3], const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
-                           const uint8_t *d_strength, void *d_out, const uint64_t *d_out_off, uint32_t n, const uint8_t *password,
-                           uint32_t password_len, uint32_t *d_out_len, int32_t *d_status, void *stream) {
+// a lane per entry -- on the way in behind the CTR kernel: it authenticates the ciphertext that kernel wrote; d_salt is the
+// write side's (null on the way in)
+int32_t wzaes_batch(const Kernel<WzaesArgs> (&k)[3], const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                    const uint8_t *d_strength, const uint8_t *d_salt, void *d_out, const uint64_t *d_out_off, uint32_t n,
+                    const uint8_t *password, uint32_t password_len, uint32_t *d_out_len, int32_t *d_status, void *stream) {
     if (!password || password_len > MZ_WZAES_PW_MAX) return MZ_CRYPT_PARAM_ERROR;
     if (n == 0) return 0;
     if (n > 0x3FFFFFFFu) return MZ_CRYPT_PARAM_ERROR; /* four lane slots per entry in a 32-bit thread index */
     Launch L;
     int32_t rc = L.begin(stream);
     if (rc) return rc;
+    WzaesArgs a{}; /* (the password's unused bytes are zero with it) */
     set_fields(a, L.c, d_in, d_in_off, d_in_len, d_out, d_out_off, nullptr, n, d_out_len, nullptr, nullptr, d_status);
     a.strength = d_strength;
+    a.salt = d_salt;
     a.password_len = password_len;
-    memset(a.password, 0, sizeof(a.password));
     memcpy(a.password, password, password_len);
     a.counter = L.head.p;
     ScratchLease sc;
@@ -208,6 +202,38 @@ int32_t wzaes_batch(A &a, const Kernel<A> (&k)[3], const void *d_in, const uint6
         le = hipGetLastError();
     }
     return launched(k[at].name, le, sc);
+}
+
+// "A wave per entry, single-wave workgroups, `per_cu` of them per CU, `stride` bytes of HBM scratch per resident wave":
+// bzip2 and Zstandard decode, bzip2 encode.  grid = min(n, resident), so a small batch costs a small scratch.
+uint32_t wave_grid(const DeviceCtx *c, uint32_t n, uint32_t per_cu) { return resident_grid(n, (uint32_t)c->cu_count * per_cu); }
+
+// behind the ..._launch_geometry calls: that grid on the current device, 0 without one or for arguments the launcher refuses
+uint32_t geometry_grid(bool args_ok, uint32_t n, uint32_t per_cu, uint32_t *grid) {
+    DeviceCtx *c = nullptr;
+    const uint32_t g = (args_ok && ctx_for_current(&c) == 0) ? wave_grid(c, n, per_cu) : 0u;
+    if (grid) *grid = g;
+    return g;
+}
+
+// the launcher: `a` arrives value-initialised with the kernel's own fields set; table, head, scratch slice and launch are here
+template <class A>
+int32_t wave_per_entry_batch(const Kernel<A> &k, A &a, uint32_t per_cu, size_t stride, const void *d_in, const uint64_t *d_in_off,
+                             const uint32_t *d_in_len, void *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap, uint32_t n,
+                             uint32_t *d_out_len, uint32_t *d_in_used, uint32_t *d_crc, int32_t *d_status, void *stream) {
+    if (n == 0) return 0;
+    Launch L;
+    int32_t rc = L.begin(stream);
+    if (rc) return rc;
+    set_fields(a, L.c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, d_in_used, d_crc, d_status);
+    a.counter = L.head.p;
+    const uint32_t grid = wave_grid(L.c, n, per_cu);
+    ScratchLease sc;
+    rc = sc.get(&L.c->scratch, (size_t)grid * stride, L.s);
+    if (rc) return rc;
+    a.scratch = (uint8_t *)sc.p;
+    hipLaunchKernelGGL(k.fn, dim3(grid), dim3(64), 0, L.s, a);
+    return launched(k.name, hipGetLastError(), sc);
 }
 
 } // namespace
@@ -239,7 +265,7 @@ int32_t mzhip_inflate_resume_batch(const void *d_in, const uint64_t *d_in_off, c
     Launch L;
     int32_t rc = L.begin(stream);
     if (rc) return rc;
-    InflateArgs a;
+    InflateArgs a{};
     set_fields(a, L.c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, d_in_used, d_crc, d_status);
     a.counter = L.head.p;
     a.resume = (const mz_inflate_state *)d_resume;
@@ -262,7 +288,7 @@ static int32_t checksum_batch(void (*kernel)(CrcArgs), const void *d_buf, const 
     Launch L;
     const int32_t rc = L.begin(stream);
     if (rc) return rc;
-    CrcArgs a;
+    CrcArgs a{};
     a.buf = (const uint8_t *)d_buf;
     a.off = d_off;
     a.len = d_len;
@@ -295,7 +321,7 @@ static int32_t lzma_family_batch(int xz, const void *d_in, const uint64_t *d_in_
     if (rc) return rc;
     DeviceCtx *c = L.c;
     hipStream_t s = L.s;
-    LzmaArgs a;
+    LzmaArgs a{}; /* sprobs, retry_list, retry_n stay null unless the slot kernel runs */
     set_fields(a, c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, d_in_used, d_crc, d_status);
     a.max_out = d_max_out;
     a.counter = L.head.p;
@@ -307,9 +333,6 @@ static int32_t lzma_family_batch(int xz, const void *d_in, const uint64_t *d_in_
 #endif
     const uint32_t grid = resident_grid(n, resident);
     ScratchLease sc; /* 12 KiB per resident wave: the literal model's upper half for streams with lc + lp = 4 */
-    a.sprobs = nullptr;
-    a.retry_list = nullptr;
-    a.retry_n = nullptr;
 #if defined(MZ_LZMA_NO_SLOT_KERNEL)
     const bool two_step = false;
 #else
@@ -376,33 +399,18 @@ int32_t mzhip_xz_batch(const void *d_in, const uint64_t *d_in_off, const uint32_
  * scratch. */
 #define MZ_BZ_WAVES_PER_CU 8u
 
-static uint32_t bzip2_grid(const DeviceCtx *c, uint32_t n) { return resident_grid(n, (uint32_t)c->cu_count * MZ_BZ_WAVES_PER_CU); }
-
 void mzhip_bzip2_launch_geometry(uint32_t n, uint32_t *grid, uint64_t *scratch_bytes) {
-    DeviceCtx *c = nullptr;
-    uint32_t g = 0;
-    if (ctx_for_current(&c) == 0) g = bzip2_grid(c, n);
-    if (grid) *grid = g;
+    const uint32_t g = geometry_grid(true, n, MZ_BZ_WAVES_PER_CU, grid);
     if (scratch_bytes) *scratch_bytes = (uint64_t)g * MZ_BZ_SCRATCH_BYTES;
 }
 
 int32_t mzhip_bzip2_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
                           const uint64_t *d_out_off, const uint32_t *d_out_cap, uint32_t n, uint32_t *d_out_len,
                           uint32_t *d_in_used, uint32_t *d_crc, int32_t *d_status, void *stream) {
-    if (n == 0) return 0;
-    Launch L;
-    int32_t rc = L.begin(stream);
-    if (rc) return rc;
-    Bzip2Args a;
-    set_fields(a, L.c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, d_in_used, d_crc, d_status);
-    a.counter = L.head.p;
-    const uint32_t grid = bzip2_grid(L.c, n);
-    ScratchLease sc;
-    rc = sc.get(&L.c->scratch, (size_t)grid * MZ_BZ_SCRATCH_BYTES, L.s);
-    if (rc) return rc;
-    a.scratch = (uint8_t *)sc.p;
-    hipLaunchKernelGGL(k_bzip2_batch, dim3(grid), dim3(64), 0, L.s, a);
-    return launched("k_bzip2_batch", hipGetLastError(), sc);
+    static const Kernel<WaveScratchArgs> k = MZ_KERNEL(k_bzip2_batch);
+    WaveScratchArgs a{};
+    return wave_per_entry_batch(k, a, MZ_BZ_WAVES_PER_CU, MZ_BZ_SCRATCH_BYTES, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n,
+                                d_out_len, d_in_used, d_crc, d_status, stream);
 }
 
 /* zstd: the literals of a block (at most 128 KiB) are decoded into HBM, MZ_ZS_SCRATCH_BYTES = 131 328 per resident wave.
@@ -411,33 +419,18 @@ int32_t mzhip_bzip2_batch(const void *d_in, const uint64_t *d_in_off, const uint
  * grid = min(n, resident). */
 #define MZ_ZS_WAVES_PER_CU 8u
 
-static uint32_t zstd_grid(const DeviceCtx *c, uint32_t n) { return resident_grid(n, (uint32_t)c->cu_count * MZ_ZS_WAVES_PER_CU); }
-
 void mzhip_zstd_launch_geometry(uint32_t n, uint32_t *grid, uint64_t *scratch_bytes) {
-    DeviceCtx *c = nullptr;
-    uint32_t g = 0;
-    if (ctx_for_current(&c) == 0) g = zstd_grid(c, n);
-    if (grid) *grid = g;
+    const uint32_t g = geometry_grid(true, n, MZ_ZS_WAVES_PER_CU, grid);
     if (scratch_bytes) *scratch_bytes = (uint64_t)g * MZ_ZS_SCRATCH_BYTES;
 }
 
 int32_t mzhip_zstd_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
                          const uint64_t *d_out_off, const uint32_t *d_out_cap, uint32_t n, uint32_t *d_out_len,
                          uint32_t *d_in_used, uint32_t *d_crc, int32_t *d_status, void *stream) {
-    if (n == 0) return 0;
-    Launch L;
-    int32_t rc = L.begin(stream);
-    if (rc) return rc;
-    ZstdArgs a;
-    set_fields(a, L.c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, d_in_used, d_crc, d_status);
-    a.counter = L.head.p;
-    const uint32_t grid = zstd_grid(L.c, n);
-    ScratchLease sc;
-    rc = sc.get(&L.c->scratch, (size_t)grid * MZ_ZS_SCRATCH_BYTES, L.s);
-    if (rc) return rc;
-    a.scratch = (uint8_t *)sc.p;
-    hipLaunchKernelGGL(k_zstd_batch, dim3(grid), dim3(64), 0, L.s, a);
-    return launched("k_zstd_batch", hipGetLastError(), sc);
+    static const Kernel<WaveScratchArgs> k = MZ_KERNEL(k_zstd_batch);
+    WaveScratchArgs a{};
+    return wave_per_entry_batch(k, a, MZ_ZS_WAVES_PER_CU, MZ_ZS_SCRATCH_BYTES, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n,
+                                d_out_len, d_in_used, d_crc, d_status, stream);
 }
 
 /* bzip2 encode: the sort of a block's rotations needs, per resident wave and per symbol the scratch holds, two rotation
@@ -452,19 +445,14 @@ int32_t mzhip_zstd_batch(const void *d_in, const uint64_t *d_in_off, const uint3
  * batch costs a small scratch. */
 #define MZ_BZE_WAVES_PER_CU 4u
 
-static uint32_t bzip2_enc_grid(const DeviceCtx *c, uint32_t n) { return resident_grid(n, (uint32_t)c->cu_count * MZ_BZE_WAVES_PER_CU); }
-
 uint64_t mzhip_bzip2_encode_bound(uint32_t in_len, int32_t level) {
     const uint64_t digit = MZ_BZE_LEVEL(level);
     return digit ? MZ_BZE_BOUND(in_len, digit) : 0u;
 }
 
 void mzhip_bzip2_encode_launch_geometry(uint32_t n, uint32_t max_in_len, int32_t level, uint32_t *grid, uint64_t *scratch_bytes) {
-    DeviceCtx *c = nullptr;
     const uint32_t digit = MZ_BZE_LEVEL(level);
-    uint32_t g = 0;
-    if (digit && ctx_for_current(&c) == 0) g = bzip2_enc_grid(c, n);
-    if (grid) *grid = g;
+    const uint32_t g = geometry_grid(digit != 0u, n, MZ_BZE_WAVES_PER_CU, grid);
     if (scratch_bytes) *scratch_bytes = (uint64_t)g * MZ_BZE_SCRATCH_BYTES(MZ_BZE_CAP_SYMS(max_in_len, digit ? digit : 1u));
 }
 
@@ -476,49 +464,33 @@ int32_t mzhip_bzip2_encode_batch(const void *d_in, const uint64_t *d_in_off, con
         snprintf(g_err, sizeof(g_err), "mzhip_bzip2_encode_batch: level %d is not 1 .. 9 or -1", (int)level);
         return -102; /* MZ_PARAM_ERROR */
     }
-    if (n == 0) return 0;
-    Launch L;
-    int32_t rc = L.begin(stream);
-    if (rc) return rc;
-    Bzip2EncArgs a;
-    set_fields(a, L.c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, nullptr, d_crc, d_status);
-    a.counter = L.head.p;
+    static const Kernel<Bzip2EncArgs> k = MZ_KERNEL(k_bzip2_encode_batch);
+    Bzip2EncArgs a{};
     a.level = digit;
     a.cap_syms = MZ_BZE_CAP_SYMS(max_in_len, digit);
     a.scratch_stride = MZ_BZE_SCRATCH_BYTES(a.cap_syms);
-    const uint32_t grid = bzip2_enc_grid(L.c, n);
-    ScratchLease sc;
-    rc = sc.get(&L.c->scratch, (size_t)grid * a.scratch_stride, L.s);
-    if (rc) return rc;
-    a.scratch = (uint8_t *)sc.p;
-    hipLaunchKernelGGL(k_bzip2_encode_batch, dim3(grid), dim3(64), 0, L.s, a);
-    return launched("k_bzip2_encode_batch", hipGetLastError(), sc);
+    return wave_per_entry_batch(k, a, MZ_BZE_WAVES_PER_CU, (size_t)a.scratch_stride, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n,
+                                d_out_len, nullptr /* an encoder takes all of its input */, d_crc, d_status, stream);
 }
 
 int32_t mzhip_sha_batch(const void *d_buf, const uint64_t *d_off, const uint32_t *d_len, uint32_t n, uint32_t algorithm,
                         void *d_digest, void *stream) {
-    if (algorithm != 20 && (algorithm < 22 || algorithm > 25)) return MZHIP_STATUS_UNSUPPORTED;
+    /* by algorithm - 20 (mz.h:127-135 defines no 21) */
+    static const Kernel<ShaArgs> k[6] = {MZ_KERNEL(k_sha_batch<20>), {nullptr, nullptr},       MZ_KERNEL(k_sha_batch<22>),
+                                         MZ_KERNEL(k_sha_batch<23>), MZ_KERNEL(k_sha_batch<24>), MZ_KERNEL(k_sha_batch<25>)};
+    if (algorithm < 20 || algorithm > 25 || !k[algorithm - 20].fn) return MZHIP_STATUS_UNSUPPORTED;
     if (n == 0) return 0;
     DeviceCtx *c = nullptr;
     int32_t rc = ctx_for_current(&c);
     if (rc) return rc;
-    ShaArgs a;
+    ShaArgs a{};
     a.buf = (const uint8_t *)d_buf;
     a.off = d_off;
     a.len = d_len;
     a.n = n;
     a.algorithm = algorithm;
     a.digest = (uint8_t *)d_digest;
-    if (algorithm == 20)
-        hipLaunchKernelGGL(k_sha_batch<20>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
-    else if (algorithm == 24)
-        hipLaunchKernelGGL(k_sha_batch<24>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
-    else if (algorithm == 25)
-        hipLaunchKernelGGL(k_sha_batch<25>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
-    else if (algorithm == 22)
-        hipLaunchKernelGGL(k_sha_batch<22>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(k_sha_batch<23>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k[algorithm - 20].fn, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -526,8 +498,7 @@ int32_t mzhip_sha_batch(const void *d_buf, const uint64_t *d_off, const uint32_t
 int32_t mzhip_pkcrypt_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
                             const uint64_t *d_out_off, uint32_t n, const uint8_t *password, uint32_t password_len,
                             const uint32_t *d_verify, uint32_t *d_out_len, int32_t *d_status, void *stream) {
-    PkcryptArgs a;
-    return pkcrypt_batch(a, k_pkcrypt_batch, d_in, d_in_off, d_in_len, d_out, d_out_off, n, password, password_len, d_verify,
+    return pkcrypt_batch(k_pkcrypt_batch, d_in, d_in_off, d_in_len, d_out, d_out_off, n, password, password_len, d_verify, nullptr,
                          d_out_len, d_status, stream);
 }
 
@@ -535,27 +506,22 @@ int32_t mzhip_wzaes_batch(const void *d_in, const uint64_t *d_in_off, const uint
                           void *d_out, const uint64_t *d_out_off, uint32_t n, const uint8_t *password, uint32_t password_len,
                           uint32_t *d_out_len, int32_t *d_status, void *stream) {
     static const Kernel<WzaesArgs> k[3] = {MZ_KERNEL(k_wzaes_keys), MZ_KERNEL(k_wzaes_ctr), MZ_KERNEL(k_wzaes_auth)};
-    WzaesArgs a;
-    return wzaes_batch(a, k, d_in, d_in_off, d_in_len, d_strength, d_out, d_out_off, n, password, password_len, d_out_len, d_status, stream);
+    return wzaes_batch(k, d_in, d_in_off, d_in_len, d_strength, nullptr, d_out, d_out_off, n, password, password_len, d_out_len, d_status, stream);
 }
 
 int32_t mzhip_pkcrypt_encrypt_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
                                     const uint64_t *d_out_off, uint32_t n, const uint8_t *password, uint32_t password_len,
                                     const uint32_t *d_verify, const uint8_t *d_header, uint32_t *d_out_len, int32_t *d_status,
                                     void *stream) {
-    PkcryptEncArgs a;
-    a.header = d_header;
-    return pkcrypt_batch(a, k_pkcrypt_enc_batch, d_in, d_in_off, d_in_len, d_out, d_out_off, n, password, password_len,
-                         d_verify, d_out_len, d_status, stream);
+    return pkcrypt_batch(k_pkcrypt_enc_batch, d_in, d_in_off, d_in_len, d_out, d_out_off, n, password, password_len, d_verify, d_header,
+                         d_out_len, d_status, stream);
 }
 
 int32_t mzhip_wzaes_encrypt_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, const uint8_t *d_strength,
                                   const uint8_t *d_salt, void *d_out, const uint64_t *d_out_off, uint32_t n, const uint8_t *password,
                                   uint32_t password_len, uint32_t *d_out_len, int32_t *d_status, void *stream) {
-    static const Kernel<WzaesEncArgs> k[3] = {MZ_KERNEL(k_wzaes_enc_keys), MZ_KERNEL(k_wzaes_enc_ctr), MZ_KERNEL(k_wzaes_enc_auth)};
-    WzaesEncArgs a;
-    a.salt = d_salt;
-    return wzaes_batch(a, k, d_in, d_in_off, d_in_len, d_strength, d_out, d_out_off, n, password, password_len, d_out_len, d_status, stream);
+    static const Kernel<WzaesArgs> k[3] = {MZ_KERNEL(k_wzaes_enc_keys), MZ_KERNEL(k_wzaes_enc_ctr), MZ_KERNEL(k_wzaes_enc_auth)};
+    return wzaes_batch(k, d_in, d_in_off, d_in_len, d_strength, d_salt, d_out, d_out_off, n, password, password_len, d_out_len, d_status, stream);
 }
 
 int32_t mzhip_deflate_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, void *d_out,
@@ -584,8 +550,8 @@ int32_t mzh::deflate_batch_launch(const void *d_in, const uint64_t *d_in_off, co
     if (rc) return rc;
     DeviceCtx *c = L.c;
     hipStream_t s = L.s;
-    DeflateArgs a;
-    set_fields(a, c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, nullptr, d_crc, d_status);
+    DeflateArgs a{};
+    set_fields(a, c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, nullptr /* an encoder takes all of its input */, d_crc, d_status);
     a.final_flag = d_final;
     a.warm = d_warm;
     a.counter = L.head.p;
@@ -655,26 +621,48 @@ void set_lz_class(DeviceCtx *c, LzmaEncArgs &a, int32_t preset) {
     if (a.ways > 1u && !big_lds_ok(c->big_lds_tok, (const void *)k_lz_tokenize_batch, MZ_WAVES_PER_WG * (sizeof(mz_lz_tok_lds) + MZ_DEF_XHEAD_BYTES)))
         a.ways = 1u;
 }
+/* The scratch of K6's parse, laid out in one place for every launcher of it: 4 bytes of token per input position of the
+ * largest entry, for every entry (n x maxb blocks); when an entry has more than one block, as much again for the chain
+ * pass's links and 1 MiB of table per resident wave of that pass; a token count per block; three work counters; and, behind
+ * the next 256-byte boundary, `coder_bytes` for the kernel that codes the tokens (0: it needs none, and no padding). */
+struct LzScratch {
+    uint32_t chain_waves; /* waves of the chain pass, 0: no entry of more than one block */
+    size_t items, tok_words, link_words, coder_off, bytes;
+    /* the parse's pointers into a lease of `bytes` at p; the counters are zeroed and the parse is queued */
+    int32_t parse(DeviceCtx *c, hipStream_t s, LzmaEncArgs &a, void *p) const {
+        a.tok = (uint32_t *)p;
+        a.links = chain_waves ? a.tok + tok_words : nullptr;
+        a.chain_head = chain_waves ? a.links + tok_words : nullptr;
+        a.ntok = a.tok + tok_words + link_words;
+        a.counter = a.ntok + items;
+        HIP_TRY(hipMemsetAsync(a.counter, 0, 3 * sizeof(uint32_t), s));
+        launch_lz_parse(c, s, a, chain_waves);
+        return 0;
+    }
+};
+LzScratch lz_scratch(uint32_t n, uint32_t maxb, size_t coder_bytes) {
+    LzScratch l{};
+    l.items = (size_t)n * maxb;
+    l.tok_words = l.items * MZ_DEF_BLOCK;
+    l.chain_waves = maxb > 1u ? resident_grid(n, MZ_LZE_CHAIN_WAVES) : 0u;
+    l.link_words = l.chain_waves ? l.tok_words + ((size_t)l.chain_waves << MZ_LZE_FAR_HBITS) : 0u;
+    const size_t parse_bytes = (l.tok_words + l.link_words + l.items + 3u) * sizeof(uint32_t);
+    l.coder_off = (parse_bytes + 255u) & ~(size_t)255u;
+    l.bytes = coder_bytes ? l.coder_off + coder_bytes : parse_bytes;
+    return l;
+}
+uint32_t lz_blocks(uint32_t in_len) { return in_len ? (in_len + MZ_DEF_BLOCK - 1) / MZ_DEF_BLOCK : 1u; }
 /* ONE stream of `maxb` blocks for the host-buffer writers, parsed: entry 0's words are the meta block's at `base` (offsets
- * from there), `tok` has room for the tokens, the chain pass's links (as many words again) and its table, the token counts
- * and three counters; skip_blocks of history in front are linked (the segment's links point into them), not parsed */
+ * from there), `tok` has lz_scratch(1, maxb, 0).bytes of room; skip_blocks of history in front are linked (the segment's
+ * links point into them), not parsed */
 template <class Meta>
 int32_t lz_parse_one_stream(DeviceCtx *c, hipStream_t s, LzmaEncArgs &a, uint8_t *base, Meta *dm, uint32_t maxb, uint32_t skip_blocks,
                             int32_t preset, uint32_t *tok) {
     set_fields(a, c, base, &dm->in_off, &dm->in_len, base, &dm->out_off, &dm->out_cap, 1, &dm->out_len, nullptr, &dm->crc, &dm->status);
-    a.mode = nullptr;
     a.maxb = maxb;
     set_lz_class(c, a, preset);
-    a.tok = tok;
-    a.links = a.tok + (size_t)maxb * MZ_DEF_BLOCK;
-    a.chain_head = a.links + (size_t)maxb * MZ_DEF_BLOCK;
     a.skip_blocks = skip_blocks;
-    a.ntok = a.chain_head + ((size_t)1 << MZ_LZE_FAR_HBITS);
-    a.counter = a.ntok + maxb;
-    HIP_TRY(hipMemsetAsync(a.counter, 0, 3 * sizeof(uint32_t), s));
-    if (maxb <= 1u) a.links = nullptr;
-    launch_lz_parse(c, s, a, 1u);
-    return 0;
+    return lz_scratch(1, maxb, 0).parse(c, s, a, tok);
 }
 } // namespace
 extern "C" {
@@ -696,28 +684,17 @@ int32_t mzhip_lzma_encode_batch_preset(const void *d_in, const uint64_t *d_in_of
     if (rc) return rc;
     DeviceCtx *c = L.c;
     hipStream_t s = L.s;
-    LzmaEncArgs a;
-    set_fields(a, c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, nullptr, d_crc, d_status);
+    LzmaEncArgs a{};
+    set_fields(a, c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, nullptr /* an encoder takes all of its input */, d_crc, d_status);
     a.mode = d_mode;
-    a.maxb = max_in_len ? (max_in_len + MZ_DEF_BLOCK - 1) / MZ_DEF_BLOCK : 1u;
+    a.maxb = lz_blocks(max_in_len);
     set_lz_class(c, a, preset);
-    /* token scratch: 4 bytes per input position of the largest entry, for every entry; when an entry has more than one
-     * block, as much again for the chain pass's links and 1 MiB of table per resident wave of that pass */
-    const size_t items = (size_t)n * a.maxb;
-    const size_t tok_words = items * MZ_DEF_BLOCK;
-    const uint32_t chain_waves = a.maxb > 1u ? resident_grid(n, MZ_LZE_CHAIN_WAVES) : 0u;
-    const size_t link_words = chain_waves ? tok_words + ((size_t)chain_waves << MZ_LZE_FAR_HBITS) : 0u;
+    const LzScratch lay = lz_scratch(n, a.maxb, 0);
     ScratchLease sc;
-    rc = sc.get(&c->scratch, (tok_words + link_words) * sizeof(uint32_t) + items * sizeof(uint32_t) + 64, s);
+    rc = sc.get(&c->scratch, lay.bytes, s);
     if (rc) return rc;
-    a.tok = (uint32_t *)sc.p;
-    a.links = chain_waves ? a.tok + tok_words : nullptr;
-    a.chain_head = chain_waves ? a.links + tok_words : nullptr;
-    a.skip_blocks = 0;
-    a.ntok = a.tok + tok_words + link_words;
-    a.counter = a.ntok + items; /* three work counters behind the token counts */
-    HIP_TRY(hipMemsetAsync(a.counter, 0, 3 * sizeof(uint32_t), s));
-    launch_lz_parse(c, s, a, chain_waves);
+    rc = lay.parse(c, s, a, sc.p);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_lzma_rc_encode_batch, dim3(resident_grid(n, (uint32_t)c->cu_count * 9u)), dim3(64), 0, s, a); /* 17 KiB LDS per single-wave workgroup */
     return launched("k_lzma_rc_encode_batch", hipGetLastError(), sc);
 }
@@ -729,32 +706,11 @@ int32_t mzhip_lzma_encode_batch_preset(const void *d_in, const uint64_t *d_in_of
  * reads, so a wave mostly waits.  A full grid on a 256-CU device holds 514 MiB of it.  grid = min(n, resident). */
 #define MZ_ZSE_WAVES_PER_CU 8u
 
-static uint32_t zstd_enc_grid(const DeviceCtx *c, uint32_t n) { return resident_grid(n, (uint32_t)c->cu_count * MZ_ZSE_WAVES_PER_CU); }
-
-/* the bytes of one launch's scratch: tokens, links and chain tables, token counts, three counters, the coder's part */
-static size_t zstd_enc_scratch(uint32_t n, uint32_t maxb, uint32_t grid, uint32_t *chain_waves_out, size_t *tok_words_out,
-                               size_t *link_words_out, size_t *coder_off_out) {
-    const size_t items = (size_t)n * maxb;
-    const size_t tok_words = items * MZ_DEF_BLOCK;
-    const uint32_t chain_waves = maxb > 1u ? resident_grid(n, MZ_LZE_CHAIN_WAVES) : 0u;
-    const size_t link_words = chain_waves ? tok_words + ((size_t)chain_waves << MZ_LZE_FAR_HBITS) : 0u;
-    const size_t coder_off = (((tok_words + link_words + items + 3u) * sizeof(uint32_t)) + 255u) & ~(size_t)255u;
-    if (chain_waves_out) *chain_waves_out = chain_waves;
-    if (tok_words_out) *tok_words_out = tok_words;
-    if (link_words_out) *link_words_out = link_words;
-    if (coder_off_out) *coder_off_out = coder_off;
-    return coder_off + (size_t)grid * MZ_ZSE_SCRATCH_BYTES;
-}
-
 uint64_t mzhip_zstd_encode_bound(uint32_t in_len) { return MZ_ZSE_BOUND(in_len); }
 
 void mzhip_zstd_encode_launch_geometry(uint32_t n, uint32_t max_in_len, int32_t level, uint32_t *grid, uint64_t *scratch_bytes) {
-    DeviceCtx *c = nullptr;
-    uint32_t g = 0;
-    if (n && MZ_ZSE_LEVEL_OK(level) && ctx_for_current(&c) == 0) g = zstd_enc_grid(c, n);
-    if (grid) *grid = g;
-    if (scratch_bytes)
-        *scratch_bytes = g ? zstd_enc_scratch(n, max_in_len ? (max_in_len + MZ_DEF_BLOCK - 1) / MZ_DEF_BLOCK : 1u, g, nullptr, nullptr, nullptr, nullptr) : 0u;
+    const uint32_t g = geometry_grid(n && MZ_ZSE_LEVEL_OK(level), n, MZ_ZSE_WAVES_PER_CU, grid);
+    if (scratch_bytes) *scratch_bytes = g ? lz_scratch(n, lz_blocks(max_in_len), (size_t)g * MZ_ZSE_SCRATCH_BYTES).bytes : 0u;
 }
 
 int32_t mzhip_zstd_encode_batch(const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, uint32_t max_in_len,
@@ -770,30 +726,20 @@ int32_t mzhip_zstd_encode_batch(const void *d_in, const uint64_t *d_in_off, cons
     if (rc) return rc;
     DeviceCtx *c = L.c;
     hipStream_t s = L.s;
-    ZstdEncArgs z;
+    ZstdEncArgs z{};
     LzmaEncArgs &a = z.a;
-    set_fields(a, c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, nullptr, d_crc, d_status);
-    a.mode = nullptr;
-    a.maxb = max_in_len ? (max_in_len + MZ_DEF_BLOCK - 1) / MZ_DEF_BLOCK : 1u;
+    set_fields(a, c, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, n, d_out_len, nullptr /* an encoder takes all of its input */, d_crc, d_status);
+    a.maxb = lz_blocks(max_in_len);
     set_lz_class(c, a, MZ_ZSE_PRESET(level));
-    const uint32_t grid = zstd_enc_grid(c, n);
-    uint32_t chain_waves = 0;
-    size_t tok_words = 0, link_words = 0, coder_off = 0;
-    const size_t bytes = zstd_enc_scratch(n, a.maxb, grid, &chain_waves, &tok_words, &link_words, &coder_off);
-    const size_t items = (size_t)n * a.maxb;
+    const uint32_t grid = wave_grid(c, n, MZ_ZSE_WAVES_PER_CU);
+    const LzScratch lay = lz_scratch(n, a.maxb, (size_t)grid * MZ_ZSE_SCRATCH_BYTES);
     ScratchLease sc;
-    rc = sc.get(&c->scratch, bytes, s);
+    rc = sc.get(&c->scratch, lay.bytes, s);
     if (rc) return rc;
-    a.tok = (uint32_t *)sc.p;
-    a.links = chain_waves ? a.tok + tok_words : nullptr;
-    a.chain_head = chain_waves ? a.links + tok_words : nullptr;
-    a.skip_blocks = 0;
-    a.ntok = a.tok + tok_words + link_words;
-    a.counter = a.ntok + items; /* three work counters behind the token counts */
-    z.scratch = (uint8_t *)sc.p + coder_off;
+    z.scratch = (uint8_t *)sc.p + lay.coder_off;
     z.flags = flags;
-    HIP_TRY(hipMemsetAsync(a.counter, 0, 3 * sizeof(uint32_t), s));
-    launch_lz_parse(c, s, a, chain_waves);
+    rc = lay.parse(c, s, a, sc.p);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_zstd_encode_batch, dim3(grid), dim3(64), 0, s, z);
     return launched("k_zstd_encode_batch", hipGetLastError(), sc);
 }
@@ -816,7 +762,7 @@ hipError_t launch_find(const DeviceCtx *c, const ParFindArgs &a, hipStream_t s, 
 }
 // ... and the headers behind the candidates read to their end, a lane each: out[] / *out_count = the ones a decoder would get past
 hipError_t launch_check(const DeviceCtx *c, const ParFindArgs &f, uint32_t *out, uint32_t *out_count, hipStream_t s) {
-    ParCheckArgs a;
+    ParCheckArgs a{};
     a.in = f.in;
     a.in_len = f.in_len;
     a.cands = f.cands;
@@ -874,7 +820,7 @@ struct DevParBackend {
     }
     int32_t find_(uint32_t b0, uint32_t b1, std::vector<uint32_t> &cands) {
         HIP_TRY(hipMemsetAsync(d_count, 0, 16, s)); /* [0] found, [1] "a pointer moved" (resolve), [2] kept by the header check */
-        ParFindArgs a;
+        ParFindArgs a{};
         a.in = d_in;
         a.in_len = in_len;
         a.b0 = b0;
@@ -898,7 +844,7 @@ struct DevParBackend {
         if (n > cap + 1u) return MZHIP_PAR_BAIL;
         HIP_TRY(mz_h2d_on(s, d_bits, bits, (size_t)n * 4));
         HIP_TRY(mz_h2d_on(s, d_pos, pos, (size_t)n * 4));
-        ParBlocksArgs a;
+        ParBlocksArgs a{};
         a.in = d_in;
         a.in_len = in_len;
         a.out = d_buf;
@@ -927,7 +873,7 @@ struct DevParBackend {
         return 0;
     }
     int32_t resolve_(uint32_t hist, uint32_t total, uint32_t *rounds) {
-        ParJumpArgs a;
+        ParJumpArgs a{};
         a.out = d_buf;
         a.ptr = d_ptr;
         a.hist = hist;
@@ -1112,7 +1058,7 @@ struct DevZstdLargeBackend {
     int32_t scan(uint32_t blk_cap, std::vector<uint32_t> &recs, std::vector<uint32_t> &frms, uint32_t *hdr) {
         const double t0 = DevParBackend::now();
         if (blk_cap > cap) return -104;
-        ZstdScanArgs a;
+        ZstdScanArgs a{};
         a.in = d_in;
         a.in_len = in_len;
         a.blk_cap = blk_cap;
@@ -1136,7 +1082,7 @@ struct DevZstdLargeBackend {
         if (n == 0 || n > cap) return -104;
         if (mode == 2u && jobs[(size_t)(n - 1u) * MZ_ZSP_JOB_WORDS + MZ_ZSP_J_END] - bias > map_n) return -104;
         HIP_TRY(mz_h2d_on(s, d_jobs, jobs, (size_t)n * MZ_ZSP_JOB_WORDS * 4));
-        ZstdBlocksArgs a;
+        ZstdBlocksArgs a{};
         a.in = d_in;
         a.in_len = in_len;
         a.out = d_out;
@@ -1149,7 +1095,7 @@ struct DevZstdLargeBackend {
         int32_t rc = head.get(&c->counters, s);
         if (rc) return rc;
         a.counter = head.p;
-        const uint32_t grid = zstd_grid(c, n);
+        const uint32_t grid = wave_grid(c, n, MZ_ZS_WAVES_PER_CU);
         ScratchLease sc;
         rc = sc.get(&c->scratch, (size_t)grid * MZ_ZS_SCRATCH_BYTES, s);
         if (rc) return rc;
@@ -1165,7 +1111,7 @@ struct DevZstdLargeBackend {
     int32_t resolve(uint32_t w0, uint32_t w1, uint32_t *rounds) {
         const double t0 = DevParBackend::now();
         if (w1 - w0 > map_n) return -104;
-        ParJumpArgs a;
+        ParJumpArgs a{};
         a.out = d_out;
         a.ptr = (uint32_t *)((uintptr_t)d_map - 4u * (uintptr_t)w0);
         a.hist = w0;
@@ -1193,7 +1139,7 @@ struct DevZstdLargeBackend {
         const double t0 = DevParBackend::now();
         if (n > cap) return -104;
         HIP_TRY(mz_h2d_on(s, d_jobs, spans, (size_t)n * 8));
-        ZstdXxhArgs a;
+        ZstdXxhArgs a{};
         a.out = d_out;
         a.spans = d_jobs;
         a.n = n;
@@ -1332,7 +1278,7 @@ int32_t mzhip_find_blocks_host(const uint8_t *in, uint32_t in_len, uint32_t b0, 
     uint8_t *base = (uint8_t *)sc.p;
     HIP_TRY(hipMemsetAsync(base, 0, in_pad + 16, MZ_HOST_STREAM));
     HIP_TRY(mz_h2d(base + misalign, in, in_len));
-    ParFindArgs a;
+    ParFindArgs a{};
     a.in = base + misalign;
     a.in_len = in_len;
     a.b0 = b0;
@@ -1483,7 +1429,7 @@ static int32_t lzma_window_host(DeviceCtx *c, const Kernel<Args> &k, const uint8
     if (hist) HIP_TRY(mz_h2d(d_buf, buf, hist));
     Args a{d_in, in_len, d_buf, buf_cap, &dm->rs, state_out ? &dm->st : nullptr, (uint16_t *)d_model,
            &dm->out_len, &dm->in_used, &dm->status, c->d_tabs};
-    set_tab64(a, c->d_tab64, 0);
+    if constexpr (std::is_same<Args, Lzma2RunArgs>::value) a.tab64 = c->d_tab64; /* the .xz block's CRC-64 */
     hipLaunchKernelGGL(k.fn, dim3(1), dim3(64), 0, MZ_HOST_STREAM, a);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail(k.name, le);
@@ -1544,13 +1490,11 @@ int32_t mzhip_lzma_encode_resume_host(const uint8_t *in, uint32_t in_len, uint32
     if (!model || !state_in || (!last && !state_out) || (uint64_t)skip_blocks * MZ_DEF_BLOCK > in_len) return -102; /* MZ_PARAM_ERROR */
     const size_t model_bytes = ((LZ_NUM_PROBS + 1u) & ~1u) * sizeof(uint16_t);
     const uint32_t cap = in_len + in_len / 8 + 1024;
-    const uint32_t maxb = in_len ? (in_len + MZ_DEF_BLOCK - 1) / MZ_DEF_BLOCK : 1u;
-    /* tokens, the chain pass's links (as many words again) and its table, the token counts, three counters */
-    const size_t tok_bytes = ((size_t)maxb * MZ_DEF_BLOCK * 2u + ((size_t)1 << MZ_LZE_FAR_HBITS)) * sizeof(uint32_t) + (size_t)maxb * sizeof(uint32_t) + 64;
+    const uint32_t maxb = lz_blocks(in_len);
     const size_t o_model = hc.take(model_bytes);
     m.in_off = hc.take(in_len, 64);
     m.out_off = hc.take(cap, 64);
-    const size_t o_tok = hc.take(tok_bytes, 64);
+    const size_t o_tok = hc.take(lz_scratch(1, maxb, 0).bytes, 64);
     m.in_len = in_len;
     m.out_cap = cap;
     memcpy(&m.rs, state_in, sizeof(m.rs));
@@ -1562,7 +1506,7 @@ int32_t mzhip_lzma_encode_resume_host(const uint8_t *in, uint32_t in_len, uint32
     if (state_in->flags & 1u) HIP_TRY(mz_h2d(d_model, model, model_bytes));
     if (in_len) HIP_TRY(mz_h2d(hc.at(m.in_off), in, in_len));
     hipStream_t s = MZ_HOST_STREAM;
-    LzmaEncResumeArgs r;
+    LzmaEncResumeArgs r{};
     rc = lz_parse_one_stream(hc.c, s, r.a, base, dm, maxb, skip_blocks, preset, (uint32_t *)hc.at(o_tok));
     if (rc) return rc;
     r.skip_blocks = skip_blocks;
@@ -1612,11 +1556,10 @@ static int32_t xz_encode_impl(const uint8_t *in, uint32_t in_len, int32_t preset
     };
     HostCall<Meta> hc;
     Meta &m = hc.m;
-    const size_t tok_words = (size_t)np * MZ_DEF_BLOCK;
     const size_t o_chunk = hc.take((size_t)np * 2 * sizeof(uint32_t), 64); /* chunk_len[np], chunk_status[np] */
     m.in_off = hc.take(in_len, 64);
     m.out_off = hc.take((size_t)np * pcap, 64);
-    const size_t o_tok = hc.take((tok_words * 2 + ((size_t)1 << MZ_LZE_FAR_HBITS) + np) * sizeof(uint32_t) + 64, 64);
+    const size_t o_tok = hc.take(lz_scratch(1, np, 0).bytes, 64);
     m.in_len = in_len;
     m.out_cap = pcap;
     int32_t rc = hc.begin();
@@ -1631,7 +1574,7 @@ static int32_t xz_encode_impl(const uint8_t *in, uint32_t in_len, int32_t preset
         HIP_TRY(mz_h2d(hc.at(m.in_off), in, in_len));
         Meta *dm = hc.dm;
         hipStream_t s = MZ_HOST_STREAM;
-        LzmaEncChunksArgs r;
+        LzmaEncChunksArgs r{};
         rc = lz_parse_one_stream(c, s, r.a, base, dm, np, 0, preset, (uint32_t *)hc.at(o_tok));
         if (rc) return rc;
         r.nchunks = np;
@@ -1797,7 +1740,7 @@ static int32_t deflate_segment_host(const uint8_t *in, uint32_t in_len, uint32_t
                 dst[i] = at;
                 at += h_out_len[i];
             }
-            PiecePackArgs pa;
+            PiecePackArgs pa{};
             pa.src = base;
             pa.src_off = d_out_off;
             pa.len = d_out_len;
