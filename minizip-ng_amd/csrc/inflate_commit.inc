@@ -1,76 +1,53 @@
 /* inflate_commit.inc -- one chunk of K1's span path leaves LDS: far copies, near copies, store, CRC.
  * Textually included by inflate_emit.inc (mz_chase_emit) after the emit wrote the chunk into the pool:
  *   literals      at their staging byte (stg[sb + r] <-> out[out_pos + r], sb = the 16-byte misalignment of out + out_pos),
- *   back-refs     as list entries lst[-(j + 1)], j < Tm, in stream order: staging index (12 bits) | (length - 1) << 12
- *                 (5 bits, pieces of at most 32 bytes) | (distance - 1) << 17.
- * Expects (wave-uniform) sb, Tb = bytes of the chunk, Tm = list entries, stg, lst, pool0, P(bad) (a lane saw a distance
- * reaching in front of the entry) and `fail`; on success the bytes are in out[], out_pos has moved and the CRC is folded
- * that far; with fail set nothing has left LDS.
- *   far       pieces (or their leading part) whose source is older than the chunk are fetched from the output
- *             buffer, 64 at a time, each lane its own, with up to four 8-byte loads in flight; what remains of a
- *             piece (source inside the chunk) is written back to the list, compacted.  (Two pieces per lane in flight,
- *             near copies with all loads first, two near pieces per lane: each measured 3.6 - 4.4 % SLOWER in round 5,
- *             profiles/r5/call1_probe.log -- and again once the wave's control had become scalar: loads first -5 %, two
- *             far batches in flight +0.9 % on 64 KiB entries and -1.8 % on 8 KiB, call15 / call16 -- more instructions buy
- *             nothing here, the kernel is bound by issue slots);
- *   near      64 remaining pieces per lane slot at a time; a piece is copied (8 bytes per step, LDS to LDS) as soon as
+ *   back-refs     as list entries of two lists, staging index (12 bits) | (length - 1) << 12 (5 bits, pieces of at most 32
+ *                 bytes) | (distance - 1) << 17: the near list lst[-(j + 1)], j < Tnear, in stream order (sources inside
+ *                 the chunk), and behind it the far list lst[-(Tnear + f + 1)], f < Tfar, in no order (sources older than
+ *                 the chunk).  A piece that is part far, part near is an entry of each.
+ * Expects (wave-uniform) sb, Tb = bytes of the chunk, Tfar / Tnear = list entries, stg, lst, pool0, P(bad) (a lane saw a
+ * distance reaching in front of the entry) and `fail`; on success the bytes are in out[], out_pos has moved and the CRC is
+ * folded that far; with fail set nothing has left LDS.
+ *   far       the entries of the far list are fetched from the output buffer, 64 at a time, each lane its own, with up
+ *             to four 8-byte loads in flight;
+ *   near      64 entries of the near list at a time; a piece is copied (8 bytes per step, LDS to LDS) as soon as
  *             no piece that writes a byte of its source is unfinished -- the rounds follow the true dependency depth
  *             inside the batch (tests/study/flush_rounds.c);
- *   store     16 bytes per lane, head and tail bytes by single lanes. */
+ *   store     16 bytes per lane, head and tail bytes by single lanes.
+ * (Measured and dropped: two far pieces per lane in flight, near copies with all loads first, two near pieces per lane: each
+ * 3.6 - 4.4 % SLOWER in round 5, profiles/r5/call1_probe.log -- and again once the wave's control had become scalar: loads
+ * first -5 %, two far batches in flight +0.9 % on 64 KiB entries and -1.8 % on 8 KiB, call15 / call16 -- more instructions
+ * buy nothing here, the kernel is bound by issue slots) */
 {
     MZ_WAVE_SYNC();
     uint8_t *const gdst = out + out_pos;
-    MZ_STAT(10, Tb); MZ_STAT(12, Tm); MZ_STAT(15, 1);
+    MZ_STAT(10, Tb); MZ_STAT(12, Tfar + Tnear); MZ_STAT(15, 1);
     {
         uint64_t badm;
         MZ_BALLOT(badm, P(bad) != 0u);
         if (badm) fail = 1; /* nothing of the chunk has left LDS: the step loop meets the token and reports it in stream order */
     }
-    /* far: sources older than the chunk; what remains of a piece goes back to the list, compacted */
-    uint32_t nnear = 0;
-    for (uint32_t b = 0; b < Tm && !fail; b += 64u) {
+    /* far: the far list alone.  Its entries write staging bytes of their own and read only the output buffer, so one
+     * MZ_WAVE_SYNC behind the whole stage is enough: it is for the near pieces, which read bytes that far pieces wrote.
+     * (Every entry through a far batch that wrote its near rest back to the list, compacted: 435.3 - 442.8 against 444.7 - 452.0
+     * GiB/s on config 2, profiles/r12; fe43378 is the last commit that builds it) */
+    const uint32_t nnear = Tnear;
+    for (uint32_t b = 0; b < Tfar && !fail; b += 64u) {
         MZ_STAT(26, 1); /* far batches */
-        PV(uint32_t, e0);
-        PV(uint32_t, rem);
+#if !(MZ_ABLATE & 3)
         MZ_LANES {
-            mz_piece32 pc;
             const uint32_t j = b + (uint32_t)lane;
-            uint32_t en = 0, rm = 0, nf = 0, si = 0;
-            if (j < Tm) {
-                en = lst[-(int32_t)(j + 1u)];
-                si = en & 0xFFFu;
-                const uint32_t ln = mz_bfe(en, 12, 5) + 1u, dist = (en >> 17) + 1u;
-                const uint32_t dstw = si - sb;
-                if (dist > dstw) {
-                    nf = dist - dstw;
-                    if (nf > ln) nf = ln;
-#if !(MZ_ABLATE & 3)
-                    mz_copy32_load(&pc, gdst - (dist - dstw) /* >= out: checked in the emit walk */, nf);
-#endif
-                }
-                rm = ln - nf;
-                MZ_STAT(21, (nf != 0u && rm != 0u) ? 1u : 0u); /* a piece split between far and near */
-                en = (en & 0xFFFE0000u) | (si + nf) | ((rm - 1u) << 12); /* what is left (only kept when rm > 0) */
+            if (j < Tfar) {
+                mz_piece32 pc;
+                const uint32_t en = lst[-(int32_t)(Tnear + j + 1u)];
+                const uint32_t si = en & 0xFFFu, nf = mz_bfe(en, 12, 5) + 1u, dist = (en >> 17) + 1u;
+                mz_copy32_load(&pc, gdst - (dist - (si - sb)) /* >= out: checked in the emit; nf <= dist - (si - sb) */, nf);
+                mz_copy32_store(&pc, stg + si, nf);
             }
-            P(e0) = en;
-            P(rem) = rm;
-#if !(MZ_ABLATE & 3)
-            if (nf) mz_copy32_store(&pc, stg + si, nf);
-#else
-            (void)pc;
+        }
 #endif
-        }
-        MZ_WAVE_SYNC(); /* every lane has read its entry: the compacted ones may overwrite them */
-        {
-            uint64_t nm;
-            MZ_BALLOT(nm, P(rem) != 0u);
-            MZ_LANES {
-                if (P(rem) != 0u) lst[-(int32_t)(nnear + MZ_RANK_BELOW(nm) + 1u)] = P(e0);
-            }
-            nnear += mz_popc64(nm);
-        }
-        MZ_WAVE_SYNC();
     }
+    MZ_WAVE_SYNC();
     MZ_STAT(13, nnear);
     MZ_PROF_MARK(6); /* far */
     /* near: sources inside the chunk, in dependency order.  The pieces of a batch lie in stream order, so the ones whose

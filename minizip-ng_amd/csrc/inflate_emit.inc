@@ -1,7 +1,8 @@
 /* inflate_emit.inc -- the second half of K1's chase window (inflate_chase.inc): the records of the chain become bytes.
  *   emit     the records are taken MZ_EMIT_GROUP at a time by 64 lanes in stream order (a lane finds its group by a binary
  *            search in the prefix sums of the lanes' group counts, tables in LDS), counted, prefix-summed, cut where the
- *            pool is full and written as staging bytes / back-reference pieces of <= 32 bytes;
+ *            pool is full and written as staging bytes / back-reference pieces of <= 32 bytes, each piece classed by where its
+ *            source lies and entered in the far list, the near list, or (split) both;
  *   commit   inflate_commit.inc: far copies (sources older than the chunk, from the output buffer), near copies (sources
  *            inside the chunk, in dependency order), the store, the CRC-32 fold.
  * A function of its own, not inlined (see inflate_walk.inc): what it keeps alive is the round's records and counters, not
@@ -132,43 +133,74 @@ MZ_DEV_NOINLINE mz_emit_result mz_chase_emit(mz_lds_handle L_, uint32_t sub_used
         const uint32_t in_ = P(kq)[(r_)] ? 1u : 0u;                                          \
         const uint32_t ln_ = P(kq)[(r_)] >> 8;
         PV(uint32_t, lby);
-        PV(uint32_t, lpc);
         PV(uint32_t, lbt);
         MZ_LANES {
-            uint32_t by = 0, pc = 0, bt = 0;
+            uint32_t by = 0, bt = 0;
 #pragma unroll
             for (uint32_t r = 0; r < MZ_EMIT_GROUP; r++) {
                 MZ_CHASE_REC(r, in, rc, ln)
                 (void)in;
                 by += ln + (rc >> 31);
-                pc += (ln > 1u) ? (ln + 31u) >> 5 : 0u;
                 bt += P(kq)[r] & 63u;
             }
             P(lby) = by;
-            P(lpc) = pc;
             P(lbt) = bt;
         }
         PV(uint32_t, sib);
-        PV(uint32_t, sim);
         MZ_INCL_SCAN(sib, lby);
-        MZ_INCL_SCAN(sim, lpc);
-        /* what fits the pool: staging bytes from the front, 4 bytes per piece from the back, 12 bits of staging index.
-         * Both sums are monotone, so the lanes that fit entirely are a run from lane 0. */
+        /* Every piece of <= 32 bytes is classed by where its source lies, now that the byte scan has placed it: dw = its
+         * offset in the chunk (staging index - sb), nfar = min(max(dist - dw, 0), len) of its bytes are older than the chunk.
+         *   far only    nfar == len   one far entry;
+         *   near only   nfar == 0     one near entry;
+         *   split       otherwise     a far entry for the first nfar bytes and a near entry for the rest, at staging index
+         *                             + nfar with the same distance.
+         * A match of L bytes (pieces at 32 k, all with the match's distance) has nfar = min(max(dist - dw, 0), L) far bytes in
+         * front: (nfar + 31) / 32 of its pieces have a far part, and, when nfar < L, all but its first nfar / 32 a near one.
+         * The two counts of a lane are summed together, far | near << 16 (a round holds at most 64 x 8 x 10 entries). */
+#define MZ_CHASE_NFAR(dist_, dw_, ln_) (((dist_) > (dw_)) ? (((dist_) - (dw_) < (ln_)) ? (dist_) - (dw_) : (ln_)) : 0u)
+        PV(uint32_t, lfn);
+        MZ_LANES {
+            uint32_t dw = P(sib) - P(lby), fn = 0;
+#pragma unroll
+            for (uint32_t r = 0; r < MZ_EMIT_GROUP; r++) {
+                MZ_CHASE_REC(r, in, rc, ln)
+                (void)in;
+                dw += rc >> 31;
+                if (ln > 1u) {
+                    const uint32_t dist = mz_bfe(rc, 16, 15) + 1u;
+                    const uint32_t nfar = MZ_CHASE_NFAR(dist, dw, ln);
+                    fn += ((nfar + 31u) >> 5) + ((nfar < ln) ? (((ln + 31u) >> 5) - (nfar >> 5)) << 16 : 0u);
+                }
+                dw += ln;
+            }
+            P(lfn) = fn;
+        }
+        PV(uint32_t, sfn);
+        MZ_INCL_SCAN(sfn, lfn);
+        /* what fits the pool: staging bytes from the front, 4 bytes per list entry (far and near) from the back, 12 bits of
+         * staging index.  The need is exact: split pieces are counted twice.  Both sums are monotone, so the lanes that fit
+         * entirely are a run from lane 0, and a round with many split pieces only takes fewer lanes. */
 #define MZ_CHASE_FITS(B_, M_) ((B_) <= 4096u && (B_) + 4u * (M_) + 48u <= pool_bytes)
         uint64_t nofit;
-        MZ_BALLOT(nofit, !MZ_CHASE_FITS(sb + P(sib), P(sim)));
-        /* the round takes whole lanes: lanes 0 .. cut - 1 (lane 0's eight records always fit an empty pool: 8 x 259 bytes and
-         * 72 pieces are 2.7 KB of the >= 5 KB a pool has).  Round 4 let the cut lane take a prefix of its records, counted
-         * once more record by record in every lane on every round: ~100 instructions a round to fill the pool's last 26 bytes */
+        MZ_BALLOT(nofit, !MZ_CHASE_FITS(sb + P(sib), (P(sfn) & 0xFFFFu) + (P(sfn) >> 16)));
+        /* the round takes whole lanes: lanes 0 .. cut - 1 (lane 0's eight records always fit an empty pool, with every piece
+         * that can be split split: 15 + 8 x 259 bytes and 8 x (9 + 1) entries -- the pieces of one match share its distance,
+         * so at most one of them is split -- are 2 087 + 320 + 48 = 2 455 bytes of the >= 5 104 a pool has).  Round 4 let the
+         * cut lane take a prefix of its records, counted once more record by record in every lane on every round: ~100
+         * instructions a round to fill the pool's last 26 bytes */
         const uint32_t cut = nofit ? mz_ctz64(nofit) : 64u;
         PV(uint32_t, acc); /* record slots of this lane that are taken */
-        uint32_t Tb, Tm, Tbits;
+        uint32_t Tb, Tfar, Tnear, Tbits;
         MZ_LANES {
             P(acc) = ((uint32_t)lane < cut) ? MZ_EMIT_GROUP : 0u;
             if ((uint32_t)lane >= cut) P(lbt) = 0u;
         }
         Tb = MZ_READLANE(sib, (cut ? cut : 1u) - 1u);
-        Tm = MZ_READLANE(sim, (cut ? cut : 1u) - 1u);
+        {
+            const uint32_t t = MZ_READLANE(sfn, (cut ? cut : 1u) - 1u);
+            Tfar = t & 0xFFFFu;
+            Tnear = t >> 16;
+        }
 #undef MZ_CHASE_FITS
         MZ_WAVE_SUM(Tbits, lbt);
         if (cut == 0u || Tbits == 0u || Tb > out_cap - out_pos) {
@@ -177,10 +209,21 @@ MZ_DEV_NOINLINE mz_emit_result mz_chase_emit(mz_lds_handle L_, uint32_t sub_used
             break;
         }
         /* write the round: literals to their staging byte, back-references as pieces of <= 32 bytes */
-        uint64_t longm; /* lanes that hold a back-reference of more than 32 bytes (rare) */
+        /* Near entries at lst[-(j + 1)], j < Tnear, in stream order (the lane's first index is its exclusive sum: the rank
+         * searches of the near stage rely on sorted starts and ends); far entries behind them at lst[-(Tnear + f + 1)],
+         * f < Tfar, in whatever order the same sums give.  A piece of p_ bytes at staging index i_, its first f_ bytes far: */
+#define MZ_CHASE_PIECE(i_, p_, f_)                                                                          \
+        {                                                                                                   \
+            const uint32_t pf_ = ((f_) < (p_)) ? (f_) : (p_);                                               \
+            MZ_STAT(21, (pf_ != 0u && pf_ < (p_)) ? 1u : 0u); /* a piece split between far and near (counted where it is  \
+                                                                 classed: also in a round that P(bad) then refuses) */      \
+            if (pf_ != 0u) lst[-(int32_t)(++fi)] = (i_) | ((pf_ - 1u) << 12) | dd;                          \
+            if (pf_ < (p_)) lst[-(int32_t)(++ni)] = ((i_) + pf_) | (((p_) - pf_ - 1u) << 12) | dd;          \
+        }
         MZ_LANES {
             uint32_t bd = 0;
-            uint32_t pos = sb + P(sib) - P(lby), mi = P(sim) - P(lpc);
+            uint32_t pos = sb + P(sib) - P(lby);
+            uint32_t fi = Tnear + ((P(sfn) - P(lfn)) & 0xFFFFu), ni = (P(sfn) - P(lfn)) >> 16; /* entries in front of the lane's */
 #pragma unroll
             for (uint32_t r = 0; r < MZ_EMIT_GROUP; r++) {
                 MZ_CHASE_REC(r, in, rc, ln)
@@ -189,47 +232,25 @@ MZ_DEV_NOINLINE mz_emit_result mz_chase_emit(mz_lds_handle L_, uint32_t sub_used
                     if (ln == 1u) {
                         stg[pos] = (uint8_t)(rc >> 8);
                     } else if (ln > 1u) {
-                        const uint32_t dist = mz_bfe(rc, 16, 15) + 1u;
-                        bd |= (dist > out_pos + (pos - sb)) ? 1u : 0u; /* invalid distance too far back */
-                        /* the first piece here; the others (a match of more than 32 bytes) below, when there are any */
-                        lst[-(int32_t)(mi + 1u)] = pos | ((((ln < 32u) ? ln : 32u) - 1u) << 12) | ((dist - 1u) << 17);
-                        mi += (ln + 31u) >> 5;
+                        const uint32_t dist = mz_bfe(rc, 16, 15) + 1u, dd = (dist - 1u) << 17;
+                        const uint32_t dw = pos - sb;
+                        const uint32_t nfar = MZ_CHASE_NFAR(dist, dw, ln);
+                        bd |= (dist > out_pos + dw) ? 1u : 0u; /* invalid distance too far back */
+                        MZ_CHASE_PIECE(pos, (ln < 32u) ? ln : 32u, nfar)
+                        /* the other pieces of a match of more than 32 bytes, same distance, in a branch of those lanes alone: 3.4 %
+                         * of the bench corpus's matches at level 6 are that long, and 94 % of its chunks hold one */
+                        if (ln > 32u) {
+                            MZ_NOUNROLL
+                            for (uint32_t o = 32u; o < ln; o += 32u) MZ_CHASE_PIECE(pos + o, (ln - o < 32u) ? ln - o : 32u, (nfar > o) ? nfar - o : 0u)
+                        }
                     }
                     pos += ln;
                 }
             }
             P(bad) = bd;
         }
-        {
-            PV(uint32_t, lng);
-            MZ_LANES {
-                uint32_t m = 0;
-#pragma unroll
-                for (uint32_t r = 0; r < MZ_EMIT_GROUP; r++) m |= ((P(kq)[r] >> 8) > 32u) ? 1u : 0u;
-                P(lng) = (P(acc) != 0u) ? m : 0u;
-            }
-            MZ_BALLOT(longm, P(lng) != 0u);
-        }
-        if (longm) {
-            MZ_LANES {
-                uint32_t pos = sb + P(sib) - P(lby), mi = P(sim) - P(lpc);
-#pragma unroll
-                for (uint32_t r = 0; r < MZ_EMIT_GROUP; r++) {
-                    MZ_CHASE_REC(r, in, rc, ln)
-                    if (in && r < P(acc)) {
-                        pos += rc >> 31;
-                        if (ln > 1u) {
-                            const uint32_t dist = mz_bfe(rc, 16, 15) + 1u;
-                            MZ_NOUNROLL
-                            for (uint32_t o = 32u; o < ln; o += 32u) /* pieces of <= 32 bytes, same distance */
-                                lst[-(int32_t)(mi + (o >> 5) + 1u)] = (pos + o) | ((((ln - o < 32u) ? ln - o : 32u) - 1u) << 12) | ((dist - 1u) << 17);
-                            mi += (ln + 31u) >> 5;
-                        }
-                        pos += ln;
-                    }
-                }
-            }
-        }
+#undef MZ_CHASE_PIECE
+#undef MZ_CHASE_NFAR
 #undef MZ_CHASE_REC
         MZ_PROF_MARK(13); /* emit */
 #include "inflate_commit.inc"
